@@ -1,6 +1,6 @@
 """bench.py -- chunks/sec of the online retrieve -> attend -> refine path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--config C2|C3|C4|C5] [--db PATCHES]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--config C2|C3|C4|C5] [--db PATCHES] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 One "step" = one pass of the whole hot path over a batch of B synthetic 64^3 chunks per GPU (steps are software-pipelined through
@@ -11,7 +11,11 @@ per-shard candidate keys when N > 1) -> same-scene demotion -> patch gather -> r
 the timed region; weights are random-init (torch.manual_seed(0)), data synthetic (no datasets / checkpoints here).
 
 Workload at N=1 (default): BASELINE.json configs[1] -- ShapeNetV2 super-res 008->064, synthetic batch, K=4, DB=50k patches.
-Prints ONE JSON line (rank 0) with the bench contract fields plus
+Prints ONE JSON line (rank 0) with the bench contract fields (metric, value, unit, higher_is_better, dtype, ms_per_step = milliseconds of one
+timed step).  A plain run does only what that line needs: set-up, spin-up and W warm-up steps, the K timed steps, the line.  --dump-outputs DIR
+then writes the df of the last timed step (rank 0's batch; a seeded sample of whole chunks above 64 MB) as DIR/df.npy.  With --full it adds
+  blocks        K further steps timed again, --repeats times; unpipelined: the same K steps through refine() one after the other
+  collectives   per-rank timings of the two collectives (N > 1 or --force-collectives)
   roofline      the dominant kernel, timed live with HIP events on its launch stream inside the timed region
   cpu_baseline  the oracle (a CPU port of the reference path) timed on the host cores (N=1 only)
   recall_at_k   the exact search against a float64 brute force on a query subset of the bench batch (k = 1, 4, 8)
@@ -48,24 +52,33 @@ F16_MFMA_PEAK_TFLOPS = 2500.0      # dense f16/bf16 MFMA peak, same guide ("~2.5
 def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
-    ap.add_argument('--steps', type=int, default=100)
-    ap.add_argument('--warmup', type=int, default=3)
+    ap.add_argument('--steps', type=int, default=100, help='timed steps (`value` and `ms_per_step` are of these)')
+    ap.add_argument('--warmup', type=int, default=3, help='untimed steps right before them')
     ap.add_argument('--batch', type=int, default=32, help='64^3 chunks per GPU per step')
     ap.add_argument('--config', default='C2')
     ap.add_argument('--db', type=int, default=0, help='database patches (default: the config\'s)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-extras', action='store_true', help='skip recall / parity / kernel table / batch sweep (profiling runs)')
-    ap.add_argument('--feature-cache', action='store_true', help='also time the optional cached-retrieval-features serving mode (reported separately)')
-    ap.add_argument('--repeats', type=int, default=4, help='further blocks of K steps timed after the contract\'s K (reported as `blocks`: min / median; never `value`)')
-    ap.add_argument('--cpu-chunks', type=int, default=0, help='chunks for the CPU baseline sample (0 = sized to ~15 s)')
-    ap.add_argument('--kernels-top', type=int, default=8, help='rows of the serial per-kernel table')
+    ap.add_argument('--full', action='store_true', help='also measure and check everything beyond the headline figure: serial per-kernel table and roofline, '
+                                                        'repeat blocks, unpipelined steps, collective timings, recall, parity, CPU baseline, batch sweep, host I/O, '
+                                                        'scene driver (a plain run sets up, warms up, times --steps steps and prints the line)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='write what the last timed step returned (df, float32) as DIR/<name>.npy')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='(--full) skip the CPU baseline')
+    ap.add_argument('--no-extras', action='store_true', help='(--full) skip recall / parity / batch sweep / host I/O / scene driver (profiling runs)')
+    ap.add_argument('--feature-cache', action='store_true', help='(--full) also time the optional cached-retrieval-features serving mode (reported separately)')
+    ap.add_argument('--repeats', type=int, default=4, help='(--full) further blocks of K steps timed after the contract\'s K (reported as `blocks`: min / median; never `value`)')
+    ap.add_argument('--cpu-chunks', type=int, default=0, help='(--full) chunks for the CPU baseline sample (0 = sized to ~15 s)')
+    ap.add_argument('--kernels-top', type=int, default=8, help='(--full) rows of the serial per-kernel table')
     ap.add_argument('--force-collectives', action='store_true', help='dev: with one rank, still run the all-gather + all-to-all + merge protocol over RCCL')
     ap.add_argument('--half-store', action='store_true', help='insist on the float16 voxel store (the default already keeps it as float16 -- the reference\'s own scene precision -- whenever every voxel survives the round trip: same gathered bits, half the bytes)')
     ap.add_argument('--fp32-store', action='store_true', help='keep the replicated voxel store as float32')
     ap.add_argument('--isotropic-db', action='store_true', help='database embeddings as isotropic unit Gaussians (rounds 1-5) instead of laid where the query encoder puts synthetic chunks')
     ap.add_argument('--ranks-share-gpu', action='store_true', help='dev: every rank on cuda:0 with the collectives over gloo (RCCL refuses two ranks on one device): runs the whole multi-rank bench on a one-GPU box; the line says so and is no scaling measurement')
     ap.add_argument('--resident-batches', type=int, default=4, help='distinct resident input batches rotated through the timed loop')
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error('--steps must be >= 1')
+    if args.feature_cache and not args.full:
+        ap.error('--feature-cache is a measurement beyond the headline: add --full')
+    return args
 
 
 def free_port():
@@ -548,6 +561,25 @@ def host_io_rate(eng, raws_host, device, steps=10):
             'every step (copy stream, double buffered); measured, not the headline metric'}
 
 
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(out_dir, df):
+    """What the last timed step returned -- the refined TSDF df [B, 1, 64, 64, 64] float32 -- as out_dir/df.npy.  Above DUMP_LIMIT_BYTES a fixed, seeded
+    sample of whole chunks is written instead, in ascending order, and their batch positions (float64) as out_dir/df_chunks.npy."""
+    out_dir.mkdir(parents=True, exist_ok=True)
+    df = df.detach().float().cpu().numpy()
+    per_chunk = df[0].nbytes
+    if df.nbytes > DUMP_LIMIT_BYTES:
+        keep = DUMP_LIMIT_BYTES // (per_chunk + 8)
+        chunks = np.sort(np.random.default_rng(0).choice(df.shape[0], size=keep, replace=False))
+        np.save(out_dir / 'df_chunks.npy', chunks.astype(np.float64))
+        df = df[chunks]
+    else:
+        (out_dir / 'df_chunks.npy').unlink(missing_ok=True)          # (left by an earlier, larger run into the same directory)
+    np.save(out_dir / 'df.npy', np.ascontiguousarray(df))
+
+
 def main():
     argv = sys.argv[1:]
     args = parse(argv)
@@ -590,13 +622,21 @@ def main():
     n_patches = args.db or cfg['db_patches']
     B, K = args.batch, cfg['K']
 
+    inputs = {}
+
+    def chunk_input(seed):
+        """synthetic.make_chunk(seed)['input_raw'], generated once per seed (the anchor chunks and the resident batches share seeds)"""
+        if seed not in inputs:
+            inputs[seed] = synthetic.make_chunk(seed, cfg)['input_raw']
+        return inputs[seed]
+
     torch.manual_seed(0)
     eng = RefinementEngine(cfg, device, None)
     # the database's embeddings are laid where the query encoder puts synthetic chunks (rank- and world-independent anchor chunks: every rank builds the same rows)
     anchors, anchors_note = None, 'isotropic unit Gaussians'
     if not args.isotropic_db:
         with torch.no_grad():
-            anchors = torch.cat([eng.embed_queries(torch.from_numpy(np.stack([synthetic.make_chunk(10_000 + a0 + b, cfg)['input_raw'] for b in range(32)])).to(device))
+            anchors = torch.cat([eng.embed_queries(torch.from_numpy(np.stack([chunk_input(10_000 + a0 + b) for b in range(32)])).to(device))
                                  for a0 in range(0, 128, 32)])
             # one anchor per DISTINCT embedding: a synthetic chunk's empty-space windows all embed alike (the reference's datasets drop such patches by occupancy,
             # dataset/patched_scene_dataset.py:28-32), and a clump of thousands of database rows at one point is a tie-break benchmark, not a search
@@ -618,14 +658,15 @@ def main():
         del vols
         vols = database.volumes
     database.force_collectives = force_dist
-    collective_events = [] if (world > 1 or force_dist) else None
+    collective_events = [] if args.full and (world > 1 or force_dist) else None
     eng.database = database
     # every rank refines its own B chunks (chunk-parallel replicas); inputs resident in HBM
     # R distinct batches stay resident and the loops rotate through them, so consecutive steps search for different queries and gather different database
     # patches (one batch replayed K times would fetch the same 8192 patches, 134 MB, out of the Infinity Cache every step).  Batch 0 of rank 0 is the batch
     # the parity / recall legs check against the oracle.
     R = max(1, args.resident_batches)
-    raws_all = [np.stack([synthetic.make_chunk(10_000 + (r * world + rank) * B + b, cfg)['input_raw'] for b in range(B)]) for r in range(R)]
+    raws_all = [np.stack([chunk_input(10_000 + (r * world + rank) * B + b) for b in range(B)]) for r in range(R)]
+    inputs.clear()
     raws = raws_all[0]
     batches = [torch.from_numpy(x).to(device) for x in raws_all]
     raw_dev = batches[0]
@@ -639,21 +680,21 @@ def main():
 
     # The timed loop is RefinementEngine.refine_stream: K steps = K batches, software-pipelined -- the front end of batch i + 1 (query encoder,
     # exact top-k, patch gather, U-Net backbone) is issued on a helper stream beside the back end of batch i (retrieval backbone, attention,
-    # decoder).  Every step does all of its work inside the timed region (the first front end and the last back end included); the same K steps
-    # through refine() one after the other are timed right after it and reported as `unpipelined`.
+    # decoder).  Every step does all of its work inside the timed region (the first front end and the last back end included); with --full the same K
+    # steps through refine() one after the other are timed right after it and reported as `unpipelined`.
     # Device spin-up ahead of the W warm-up steps (untimed, reported as `spinup_steps`): an idle MI355X needs a few hundred milliseconds of work to reach its
     # clocks, and the first passes also pack the weight images and grow both streams' allocator pools.  The timed region is exactly K steps after W warm-up steps.
     SPINUP = 12
     for df in eng.refine_stream(rotate(SPINUP)):
         pass
-    # roofline: WHICH launch is the dominant one is decided by a serial pass (HIP events around every C-ABI launch, one step after the other, nothing
+    # roofline (--full): WHICH launch is the dominant one is decided by a serial pass (HIP events around every C-ABI launch, one step after the other, nothing
     # overlapped: the launch with the largest mean duration among those with a roofline) -- inside the pipelined step a launch shares the CUs with the other
     # streams' kernels and its in-step duration is partly contention (round 3's C5 line named a 15x inflated launch).  THAT entry point is then bracketed
     # with HIP events on its launch stream inside the timed region: `roofline.achieved` is its algorithmic work / its mean in-step duration (the contract's
     # definition), `frac_serial` the same against its duration in the serial pass.
     from rfuse import _lib
     lib = _lib.load()
-    kernels, dominant = kernel_table(eng, raw_dev, cfg, top=args.kernels_top)
+    kernels, dominant = kernel_table(eng, raw_dev, cfg, top=args.kernels_top) if args.full else (None, None)
     for df in eng.refine_stream(rotate(args.warmup)):
         pass
     torch.cuda.synchronize()
@@ -670,34 +711,40 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     database.collective_events = None
-    lib.stop_profile()
+    if dominant is not None:
+        lib.stop_profile()
+    last_df = df                                                  # what the last timed step returned (--dump-outputs)
     # further blocks of the same K steps: box-to-box and run-to-run spread is a few percent (clocks follow the power budget), one block cannot show a 3 % change
     block_ms = [1e3 * elapsed / args.steps]
-    for _ in range(max(0, args.repeats)):
+    elapsed_plain = None
+    if args.full:
+        for _ in range(max(0, args.repeats)):
+            barrier()
+            torch.cuda.synchronize()
+            tb = time.perf_counter()
+            for df in eng.refine_stream(rotate(args.steps)):
+                pass
+            torch.cuda.synchronize()
+            barrier()
+            block_ms.append(1e3 * (time.perf_counter() - tb) / args.steps)
+        for _ in range(min(2, args.warmup)):                      # the front end's tensors now come from the main stream's allocator pool: let it grow
+            eng.refine(raw_dev)
         barrier()
         torch.cuda.synchronize()
-        tb = time.perf_counter()
-        for df in eng.refine_stream(rotate(args.steps)):
-            pass
+        t1 = time.perf_counter()
+        for x in rotate(args.steps):
+            eng.refine(x)
         torch.cuda.synchronize()
         barrier()
-        block_ms.append(1e3 * (time.perf_counter() - tb) / args.steps)
-    for _ in range(min(2, args.warmup)):                          # the front end's tensors now come from the main stream's allocator pool: let it grow
-        eng.refine(raw_dev)
-    barrier()
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    for x in rotate(args.steps):
-        eng.refine(x)
-    torch.cuda.synchronize()
-    barrier()
-    elapsed_plain = time.perf_counter() - t1
+        elapsed_plain = time.perf_counter() - t1
     t = torch.tensor([elapsed] + [m * args.steps / 1e3 for m in block_ms[1:]], dtype=torch.float64, device=device)
     if world > 1 or force_dist:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t[0].item())
     block_ms = [1e3 * float(v) / args.steps for v in t.tolist()]
     assert torch.isfinite(df).all()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(Path(args.dump_outputs), last_df)
 
     in_step = [e0.elapsed_time(e1) for name, ints, e0, e1, _ in dom_records if dominant is not None and ints[:8] == dominant[2]]
     per_rank_collectives = None
@@ -708,7 +755,7 @@ def main():
 
     # every rank computes its own recall (collective-free for world == 1; with shards the search itself is a collective)
     recall = None
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         recall = recall_at_k(eng, database, emb, raw_dev, K)
 
     if rank == 0:
@@ -790,14 +837,17 @@ def main():
                        'chunks_per_gpu_per_step': B, 'db_patches': n_patches,
                        'parallelism': 'chunk-parallel replicas x%d, DB embedding matrix sharded %d-way: RCCL all-gather of the queries + all-to-all of the packed top-2K keys' % (world, world)},
             'schedule': 'RefinementEngine.refine_stream: steps software-pipelined (front end of batch i + 1 beside the back end of batch i), U-Net backbone beside the retrieval path',
-            'blocks': {'ms_per_step': block_ms, 'min_ms': float(np.min(block_ms)), 'median_ms': float(np.median(block_ms)), 'value_at_median': world * B / (float(np.median(block_ms)) * 1e-3),
-                       'note': '`value` is the FIRST block (the contract\'s K steps after W warm-up steps); the others are the same K steps timed again, back to back (max over ranks)'},
-            'unpipelined': {'value': world * B * args.steps / elapsed_plain, 'ms_per_step': 1e3 * elapsed_plain / args.steps,
-                            'note': 'the same K steps through RefinementEngine.refine() one after the other (rank-0 clock)'},
-            'roofline': roof,
-            'kernels': kernels,
-            'recall_at_k': recall,
         }
+        if args.full:
+            out.update({
+                'blocks': {'ms_per_step': block_ms, 'min_ms': float(np.min(block_ms)), 'median_ms': float(np.median(block_ms)), 'value_at_median': world * B / (float(np.median(block_ms)) * 1e-3),
+                           'note': '`value` is the FIRST block (the contract\'s K steps after W warm-up steps); the others are the same K steps timed again, back to back (max over ranks)'},
+                'unpipelined': {'value': world * B * args.steps / elapsed_plain, 'ms_per_step': 1e3 * elapsed_plain / args.steps,
+                                'note': 'the same K steps through RefinementEngine.refine() one after the other (rank-0 clock)'},
+                'roofline': roof,
+                'kernels': kernels,
+                'recall_at_k': recall,
+            })
         out['rccl_ranks'] = dist.get_world_size() if (world > 1 or force_dist) and not args.ranks_share_gpu else 0
         out['topk_scan'] = 'VALU scan: the shard probed as clumped (PatchDatabase.scan_algo)' if database.scan_algo else 'by size: VALU scan below 4e7 (query, row) pairs, split-f16-MFMA-filtered scan above'
         if args.ranks_share_gpu:
@@ -823,7 +873,7 @@ def main():
                 database.force_collectives = True
                 out['collectives'].update(step_ms_without_collectives=plain_ms, exposed_ms_per_step=1e3 * elapsed / args.steps - plain_ms)
         state = None
-        if world == 1 and not args.no_extras:
+        if args.full and world == 1 and not args.no_extras:
             state = {n: {k: v.detach().cpu() for k, v in m.state_dict().items()} for n, m in eng.modules().items()}
             out['batch_sweep'] = batch_sweep(cfg, database, state, device)
             out['host_io'] = host_io_rate(eng, torch.from_numpy(raws), device)
@@ -843,13 +893,13 @@ def main():
                                          'note': 'optional mode, work skipped (retrieval backbone replaced by a gather of cached '
                                                  'features); not the headline metric', 'cache_bytes': int(database.feature_cache.numel() * 4)}
         host_db_ok = n_patches <= 200_000                        # the oracle needs the voxel store on the host (16 GB at 1 M patches)
-        if world == 1 and host_db_ok and not (args.no_cpu_baseline and args.no_extras):
+        if args.full and world == 1 and host_db_ok and not (args.no_cpu_baseline and args.no_extras):
             state = state or {n: {k: v.detach().cpu() for k, v in m.state_dict().items()} for n, m in eng.modules().items()}
             db_host = {'emb': emb.cpu().numpy(), 'meta': meta.numpy(), 'volumes': vols.float().cpu().numpy()}
             if not args.no_extras:
                 out['parity_max_abs'] = parity_of_bench_batch(cfg, eng, state, db_host, raws, raw_dev)
             out['cpu_baseline'] = None if args.no_cpu_baseline else cpu_baseline(cfg, state, db_host, raws, n_chunks=args.cpu_chunks)
-        else:
+        elif args.full:
             out['cpu_baseline'] = None
             if world == 1 and not host_db_ok:
                 out['cpu_baseline_note'] = 'skipped: the oracle needs the %d-patch voxel store on the host' % n_patches

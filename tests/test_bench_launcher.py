@@ -43,6 +43,37 @@ def test_launch_plan_plumbing():
         bench.launch_plan(bench.parse(['--gpus', '0']), ['--gpus', '0'], {})
 
 
+def test_plain_and_full_options():
+    """a plain run is the default; --steps sets the timed steps and must be positive; the side measurements ask for --full"""
+    bench = _bench()
+    a = bench.parse(['--steps', '7', '--warmup', '2'])
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs is None
+    assert bench.parse(['--full', '--feature-cache', '--dump-outputs', 'out']).dump_outputs == 'out'
+    for bad in (['--steps', '0'], ['--feature-cache']):
+        with pytest.raises(SystemExit):
+            bench.parse(bad)
+
+
+def test_dump_outputs(tmp_path, monkeypatch):
+    """--dump-outputs writes the step's df as float32 .npy; above the size limit a seeded sample of whole chunks (the same one every time) and their
+    batch positions"""
+    import numpy as np
+    import torch
+    bench = _bench()
+    df = torch.randn(10, 1, 4, 4, 4, generator=torch.Generator().manual_seed(0))
+    bench.dump_outputs(tmp_path / 'all', df)
+    got = np.load(tmp_path / 'all' / 'df.npy')
+    assert got.dtype == np.float32 and np.array_equal(got, df.numpy()) and not (tmp_path / 'all' / 'df_chunks.npy').exists()
+    monkeypatch.setattr(bench, 'DUMP_LIMIT_BYTES', 1000)                # 256 B per chunk: 3 chunks + their positions fit
+    for d in ('s1', 's2'):
+        bench.dump_outputs(tmp_path / d, df)
+    chunks = np.load(tmp_path / 's1' / 'df_chunks.npy')
+    got = np.load(tmp_path / 's1' / 'df.npy')
+    assert chunks.dtype == np.float64 and len(chunks) == 3 and np.all(np.diff(chunks) > 0)
+    assert np.array_equal(got, df.numpy()[chunks.astype(np.int64)]) and got.nbytes + chunks.nbytes <= 1000
+    assert np.array_equal(chunks, np.load(tmp_path / 's2' / 'df_chunks.npy')) and np.array_equal(got, np.load(tmp_path / 's2' / 'df.npy'))
+
+
 def test_rank_count_mismatch_is_refused():
     """--gpus 4 inside a 2-rank job is a launcher error, caught before any GPU work (runs without a GPU)"""
     env = dict(os.environ, WORLD_SIZE='2', RANK='0', LOCAL_RANK='0')
@@ -51,12 +82,34 @@ def test_rank_count_mismatch_is_refused():
 
 
 @pytest.mark.gpu
+def test_plain_run_prints_the_headline_and_dumps_the_last_step(tmp_path):
+    """`python bench.py --gpus 1` without --full: one JSON line with the contract fields and none of the side measurements; --dump-outputs writes the
+    df of the last timed step"""
+    import numpy as np
+    import torch
+    if not torch.cuda.is_available():
+        pytest.skip('no GPU visible')
+    env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT') and not k.startswith('RFUSE_')}
+    r = subprocess.run([sys.executable, str(REPO / 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--batch', '4', '--db', '4096',
+                        '--resident-batches', '2', '--dump-outputs', str(tmp_path / 'out')], env=env, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-4000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, r.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out['steps'] == 3 and out['value'] > 0 and out['ms_per_step'] > 0 and out['unit'] == 'chunks/s' and out['higher_is_better'] is True
+    assert abs(out['value'] - 4 * 1e3 / out['ms_per_step']) <= 1e-6 * out['value']
+    assert not {'roofline', 'kernels', 'blocks', 'unpipelined', 'recall_at_k', 'cpu_baseline', 'batch_sweep'} & set(out)
+    df = np.load(tmp_path / 'out' / 'df.npy')
+    assert df.dtype == np.float32 and df.shape == (4, 1, 64, 64, 64) and np.isfinite(df).all()
+
+
+@pytest.mark.gpu
 def test_self_launched_ranks_print_one_json_line():
     import torch
     if not torch.cuda.is_available():
         pytest.skip('no GPU visible')
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT') and not k.startswith('RFUSE_')}
-    r = subprocess.run([sys.executable, str(REPO / 'bench.py'), '--gpus', '1', '--force-collectives', '--steps', '4', '--warmup', '1', '--repeats', '0', '--batch', '4',
+    r = subprocess.run([sys.executable, str(REPO / 'bench.py'), '--gpus', '1', '--force-collectives', '--full', '--steps', '4', '--warmup', '1', '--repeats', '0', '--batch', '4',
                         '--db', '4096', '--no-extras', '--no-cpu-baseline', '--resident-batches', '2'], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -76,7 +129,7 @@ def test_two_self_launched_ranks_on_one_gpu():
     if not torch.cuda.is_available():
         pytest.skip('no GPU visible')
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT') and not k.startswith('RFUSE_')}
-    r = subprocess.run([sys.executable, str(REPO / 'bench.py'), '--gpus', '2', '--ranks-share-gpu', '--steps', '3', '--warmup', '1', '--repeats', '0', '--batch', '4',
+    r = subprocess.run([sys.executable, str(REPO / 'bench.py'), '--gpus', '2', '--ranks-share-gpu', '--full', '--steps', '3', '--warmup', '1', '--repeats', '0', '--batch', '4',
                         '--db', '4099', '--no-cpu-baseline', '--resident-batches', '2'], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -96,7 +149,7 @@ def test_the_north_star_multi_gpu_configuration_through_the_self_launcher():
     if not torch.cuda.is_available():
         pytest.skip('no GPU visible')
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT') and not k.startswith('RFUSE_')}
-    r = subprocess.run([sys.executable, str(REPO / 'bench.py'), '--gpus', '2', '--ranks-share-gpu', '--config', 'C3', '--db', '200000', '--steps', '2', '--warmup', '1',
+    r = subprocess.run([sys.executable, str(REPO / 'bench.py'), '--gpus', '2', '--ranks-share-gpu', '--full', '--config', 'C3', '--db', '200000', '--steps', '2', '--warmup', '1',
                         '--repeats', '0', '--no-cpu-baseline', '--resident-batches', '2'], env=env, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]

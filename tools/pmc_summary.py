@@ -75,7 +75,7 @@ rows.sort(reverse=True)
 
 out_csv = REPO / 'profiles' / ('%s_pmc_bench_%s_B32.csv' % (tag, cfg_name))
 with open(out_csv, 'w') as f:
-    f.write('# rocprofv3 --pmc <group> --kernel-trace -- python bench.py --config %s --steps 2 --warmup 1 --no-cpu-baseline --no-extras  (B=32 chunks/step; tools/pmc_conv.sh, summarised by tools/pmc_summary.py)\n' % cfg_name)
+    f.write('# rocprofv3 --pmc <group> --kernel-trace -- python bench.py --config %s --steps 2 --warmup 1 --full --no-cpu-baseline --no-extras  (B=32 chunks/step; tools/pmc_conv.sh, summarised by tools/pmc_summary.py)\n' % cfg_name)
     f.write('# separate passes: {SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE}, {SQ_LDS_* SQ_INSTS_*}, {FETCH_SIZE}, {WRITE_SIZE}\n')
     f.write('# per-launch averages; counters are summed over the 8 XCDs; cycles = GRBM_GUI_ACTIVE/8; mfma_busy = SQ_VALU_MFMA_BUSY_CYCLES / (cycles * 1024 SIMDs);\n')
     f.write('# fetch_MB = 2 x FETCH_SIZE KB (gfx950 correction of MI355X_MICROARCH.md, HBM section), write_MB = WRITE_SIZE KB; rows ordered by total cycles\n')
