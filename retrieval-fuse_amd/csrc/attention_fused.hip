@@ -295,8 +295,8 @@ __device__ __forceinline__ void ams_split4(const f32x4& v, am_h8& h, am_h8& l, i
     for (int e = 0; e < 4; e += 2) {
         const am_f2 s2 = (am_f2){v[e], v[e + 1]} * (am_f2){AMS_ACT, AMS_ACT};
         am_f2 x;
-        x.x = __builtin_amdgcn_fmed3f(s2.x, -65504.f, 65504.f);
-        x.y = __builtin_amdgcn_fmed3f(s2.y, -65504.f, 65504.f);
+        x.x = rf_clamp_f16(s2.x);
+        x.y = rf_clamp_f16(s2.y);
         const am_f2 xl = x * (am_f2){AMS_LO, AMS_LO};
         const _Float16 ha = (_Float16)x.x, hb = (_Float16)x.y;
         h[o + e] = ha; h[o + e + 1] = hb;
@@ -406,7 +406,7 @@ __global__ __launch_bounds__(AMS_WAVES * 64) void k_attn_mlp_split(AmArgs a) {
                     const am_f2 va = __builtin_elementwise_fma((am_f2){lo[ib][0], lo[ib][1]}, c2, (am_f2){hi[ib][0], hi[ib][1]}) + (am_f2){bz.x, bz.y};
                     const am_f2 vb = __builtin_elementwise_fma((am_f2){lo[ib][2], lo[ib][3]}, c2, (am_f2){hi[ib][2], hi[ib][3]}) + (am_f2){bz.z, bz.w};
                     const am_f2 na = va * s2, nb = vb * s2;
-                    const f32x4 v = {fmaxf(va.x, na.x), fmaxf(va.y, na.y), fmaxf(vb.x, nb.x), fmaxf(vb.y, nb.y)};
+                    const f32x4 v = {rf_max(va.x, na.x), rf_max(va.y, na.y), rf_max(vb.x, nb.x), rf_max(vb.y, nb.y)};
                     ams_split4(v, bh[ib >> 1], bl[ib >> 1], 4 * (ib & 1));
                 }
             } else {

@@ -24,7 +24,7 @@ __device__ __forceinline__ float rf_attn_row_scores(const float* __restrict__ xf
         float n2 = 0.f;
 #pragma unroll
         for (int i = 0; i < F; ++i) n2 += xv[i] * xv[i];
-        const float xden = fmaxf(sqrtf(n2), 1e-12f);
+        const float xden = rf_max(sqrtf(n2), 1e-12f);
 #pragma unroll
         for (int i = 0; i < F; ++i) xv[i] = xv[i] / xden;
 #pragma unroll
@@ -40,18 +40,18 @@ __device__ __forceinline__ float rf_attn_row_scores(const float* __restrict__ xf
                 float pn2 = 0.f;
 #pragma unroll
                 for (int i = 0; i < F; ++i) pn2 += pv[i] * pv[i];
-                const float pden = fmaxf(sqrtf(pn2), 1e-12f);
+                const float pden = rf_max(sqrtf(pn2), 1e-12f);
                 float dot = 0.f;
 #pragma unroll
                 for (int i = 0; i < F; ++i) dot += xv[i] * (pv[i] / pden);
                 sc[k] = dot;
-                smax = fmaxf(smax, dot);
+                smax = rf_max(smax, dot);
             }
         }
     } else {
         float n2 = 0.f;
         for (int i = 0; i < f; ++i) n2 += xf_row[i] * xf_row[i];
-        const float xden = fmaxf(sqrtf(n2), 1e-12f);
+        const float xden = rf_max(sqrtf(n2), 1e-12f);
 #pragma unroll
         for (int k = 0; k < RF_MAX_K; ++k) {
             sc[k] = -INFINITY;
@@ -59,11 +59,11 @@ __device__ __forceinline__ float rf_attn_row_scores(const float* __restrict__ xf
                 const float* p = pf_rows + (size_t)k * f;
                 float pn2 = 0.f;
                 for (int i = 0; i < f; ++i) pn2 += p[i] * p[i];
-                const float pden = fmaxf(sqrtf(pn2), 1e-12f);
+                const float pden = rf_max(sqrtf(pn2), 1e-12f);
                 float dot = 0.f;
                 for (int i = 0; i < f; ++i) dot += (xf_row[i] / xden) * (p[i] / pden);
                 sc[k] = dot;
-                smax = fmaxf(smax, dot);
+                smax = rf_max(smax, dot);
             }
         }
     }
@@ -74,7 +74,7 @@ __device__ __forceinline__ void rf_attn_row_weights(const float* __restrict__ xf
                                                     const float* __restrict__ noise_row, int K, int f, int mode, float sharpness,
                                                     float (&sc)[RF_MAX_K], float (&w)[RF_MAX_K], float& sw) {
     const float smax = f == 32 ? rf_attn_row_scores<32>(xf_row, pf_rows, K, f, sc) : rf_attn_row_scores<0>(xf_row, pf_rows, K, f, sc);
-    sw = fmaxf(smax, 0.f);                                    // relu(max_k scores), model/attention.py:99
+    sw = rf_relu(smax);                                      // relu(max_k scores), model/attention.py:99
     if (mode == RF_ATTN_SOFTMAX) {
         // softmax(sharpness * scores): z = sharpness*s rounded first, then exp(z - zmax) / sum as torch does
         const float zmax = sharpness * smax;

@@ -87,6 +87,22 @@ __device__ __forceinline__ float wave_sum(float v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
+// Max, ReLU and the split operands' f16-range clamp of the forward kernels, NaN-propagating like the reference (torch.relu, F.max_pool3d, fp32
+// arithmetic).  fmaxf is IEEE maxNum (v_max_f32): given one NaN it returns the other operand, so a NaN accumulator came out of a ReLU as 0 and out
+// of a max-pool as its neighbours' maximum; v_med3_f32 returns a bound for a NaN input.  For finite inputs these give the same bits as before.
+__device__ __forceinline__ float rf_max(float a, float b) { return __builtin_elementwise_maximum(a, b); }      // IEEE-754-2019 maximum: v_maximum3_f32
+__device__ __forceinline__ float rf_relu(float v) { return __builtin_elementwise_maximum(v, 0.f); }
+// clamp to [-65504, 65504]; NaN and +-inf come out as NaN.  0 * v is NaN for those and a zero of v's sign otherwise, and adding a zero of
+// v's sign to med3(v, ...) changes no finite result (-0 included): two VALU ops (v_med3_f32 + v_fma_f32), the f16 split after it keeps the NaN.
+// The fma is inline asm: as fmaf the compiler pairs it into v_pk_fma_f32 with op_sel on src1, which build.py:check_isa refuses
+__device__ __forceinline__ float rf_clamp_f16(float v) {
+    const float m = __builtin_amdgcn_fmed3f(v, -65504.f, 65504.f);
+    float r;
+    asm("v_fma_f32 %0, %1, 0, %2" : "=v"(r) : "v"(v), "v"(m));
+    return r;
+}
+
+// fmaxf (maxNum) on purpose: only the top-k scan's seed bound uses this (retrieval.hip), no forward activation does
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));

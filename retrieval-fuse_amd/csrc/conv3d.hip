@@ -193,7 +193,7 @@ __global__ __launch_bounds__(256) void k_conv3_direct(const float* __restrict__ 
                 }
             }
         }
-        out[i] = fmaxf(acc, 0.f);
+        out[i] = rf_relu(acc);
     }
 }
 
@@ -239,7 +239,7 @@ __global__ __launch_bounds__(256) void k_maxpool2(const float* __restrict__ x, s
 #pragma unroll
             for (int dy = 0; dy < 2; ++dy) {
                 const float2 v = *reinterpret_cast<const float2*>(b + ((size_t)dz * edge + dy) * edge);
-                m = fmaxf(m, fmaxf(v.x, v.y));
+                m = rf_max(m, rf_max(v.x, v.y));
             }
         dst[i] = m;
         sm += (double)m;
@@ -272,7 +272,7 @@ __global__ __launch_bounds__(256) void k_maxpool2_small(const float* __restrict_
 #pragma unroll
             for (int dy = 0; dy < 2; ++dy) {
                 const float2 v = *reinterpret_cast<const float2*>(b + ((size_t)dz * E + dy) * E);
-                m = fmaxf(m, fmaxf(v.x, v.y));
+                m = rf_max(m, rf_max(v.x, v.y));
             }
         out[plane * OV + o] = m;
     }

@@ -121,7 +121,7 @@ __global__ __launch_bounds__(256, 2) void k_conv3_e2_split(E2Args a) {
     h8 nah[2], nal[2];                                             // edge 1: converted at once (8 affines per row would not fit beside the accumulators)
     h8 wreg[8];
     auto split1 = [](float y, _Float16& hh, _Float16& ll) {
-        const float v = __builtin_amdgcn_fmed3f(y * E2_ACT_SCALE, -65504.f, 65504.f);
+        const float v = rf_clamp_f16(y * E2_ACT_SCALE);
         hh = (_Float16)v;
         ll = (_Float16)fmaf(-E2_LO, (float)hh, v * E2_LO);
     };
@@ -204,7 +204,7 @@ __global__ __launch_bounds__(256, 2) void k_conv3_e2_split(E2Args a) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int sm = n0 + (2 * wm + i) * 16 + kg * 4 + r;
-                const float y = fmaxf(fmaf(lo[i][j][r], 1.0f / E2_LO, hi[i][j][r]), 0.f);
+                const float y = rf_relu(fmaf(lo[i][j][r], 1.0f / E2_LO, hi[i][j][r]));
                 const bool live = sm < a.n && col < ncols;
                 if (live) a.out[(size_t)sm * ncols + col] = y;
                 if (a.stats) {                                      // the 8 voxels of a cout: lanes li & 7 = 0 .. 7 of the same row (wave-uniform branch)

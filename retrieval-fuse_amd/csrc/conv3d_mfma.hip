@@ -447,7 +447,7 @@ __global__ __launch_bounds__(256) void k_conv3_cin1(ConvArgs a) {
     for (int z = 0; z < TZ; ++z) {
         float* o = a.out + (size_t)nn * COUT * vol + ((size_t)(z0 + z) * edge + (y0 + y)) * edge + (x0 + x);
 #pragma unroll
-        for (int co = 0; co < COUT; ++co) o[co * vol] = fmaxf(acc[z][co], 0.f);
+        for (int co = 0; co < COUT; ++co) o[co * vol] = rf_relu(acc[z][co]);
     }
     if (a.stats) {
         // per (wave, cout) sums of the ReLU'd outputs in float64.  The 16 values of a lane (sum and sum of squares of 8 couts) are reduced over
@@ -462,7 +462,7 @@ __global__ __launch_bounds__(256) void k_conv3_cin1(ConvArgs a) {
             if (co < COUT) {
 #pragma unroll
                 for (int z = 0; z < TZ; ++z) {
-                    const double t = (double)fmaxf(acc[z][co], 0.f);
+                    const double t = (double)rf_relu(acc[z][co]);
                     sm += t; sq += t * t;
                 }
             }

@@ -302,7 +302,7 @@ __global__ __launch_bounds__(512, 4) void k_conv3_small(SmallArgs a) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int smp = wgrp * 16 + kq * 4 + r;          // D rows of this lane: samples 4*kq + r of the group
-                    eb[(li * SAMPLES + smp) * EROW + pos] = fmaxf(acc[mb][nb][r], 0.f);
+                    eb[(li * SAMPLES + smp) * EROW + pos] = rf_relu(acc[mb][nb][r]);
                 }
             }
             __syncthreads();
@@ -327,8 +327,8 @@ __global__ __launch_bounds__(512, 4) void k_conv3_small(SmallArgs a) {
 #pragma unroll
                         for (int cell = 0; cell < 8; ++cell) {
                             const int base = (cell >> 2) * 32 + ((cell >> 1) & 1) * 8 + (cell & 1) * 2;      // (2Z, 2Y, 2X)
-                            float m = fmaxf(fmaxf(e[base], e[base + 1]), fmaxf(e[base + 4], e[base + 5]));
-                            m = fmaxf(m, fmaxf(fmaxf(e[base + 16], e[base + 17]), fmaxf(e[base + 20], e[base + 21])));
+                            float m = rf_max(rf_max(e[base], e[base + 1]), rf_max(e[base + 4], e[base + 5]));
+                            m = rf_max(m, rf_max(rf_max(e[base + 16], e[base + 17]), rf_max(e[base + 20], e[base + 21])));
                             pv[cell] = m;
                             sm += (double)m; sq += (double)m * (double)m;
                         }
@@ -348,7 +348,7 @@ __global__ __launch_bounds__(512, 4) void k_conv3_small(SmallArgs a) {
                     sm[r] = 0.0; sq[r] = 0.0;
 #pragma unroll
                     for (int mb = 0; mb < MB; ++mb) {
-                        const double v = (double)fmaxf(acc[mb][nb][r], 0.f);
+                        const double v = (double)rf_relu(acc[mb][nb][r]);
                         sm[r] += v; sq[r] += v * v;
                     }
                 }

@@ -258,7 +258,7 @@ __global__ __launch_bounds__(512, WPS) void k_conv3_split(ConvArgs a, SplitPreOu
                 if constexpr (!ONE && !PRE) {
                     const int e = (s - 2) * 4 + m, r = e >> 3, j = e & 7;
                     const float y = vin[r] ? fmaf(x.x[r][j] - afn[j].x, afn[j].y, afn[j].z) : 0.f;
-                    const float v = __builtin_amdgcn_fmed3f(y * CS_ACT_SCALE, -65504.f, 65504.f);
+                    const float v = rf_clamp_f16(y * CS_ACT_SCALE);
                     const _Float16 hh = (_Float16)v;
                     hq[r][j] = hh;
                     lq[r][j] = (_Float16)fmaf(-CS_LO, (float)hh, v * CS_LO);
@@ -305,7 +305,7 @@ __global__ __launch_bounds__(512, WPS) void k_conv3_split(ConvArgs a, SplitPreOu
                     for (int r = 0; r < 4; ++r) {
                         int sdummy, z, y, x;
                         BoxOrder<8, 8, 8, 8, 4>::voxel(wave, m, 4 * (lane >> 4) + r, sdummy, z, y, x);
-                        e[col * CS_PO_STRIDE + (z * 8 + y) * 8 + x] = fmaxf(fmaf(lo[m][0][r], 1.0f / CS_LO, hi[m][0][r]), a.floor);
+                        e[col * CS_PO_STRIDE + (z * 8 + y) * 8 + x] = rf_max(fmaf(lo[m][0][r], 1.0f / CS_LO, hi[m][0][r]), a.floor);
                     }
             }
             __syncthreads();
@@ -364,7 +364,7 @@ __global__ __launch_bounds__(512, WPS) void k_conv3_split(ConvArgs a, SplitPreOu
                     for (int r = 0; r < 4; ++r) {
                         int sdummy, z, y, x;
                         BoxOrder<8, 8, 8, 8, 4>::voxel(wave, m, 4 * (lane >> 4) + r, sdummy, z, y, x);
-                        e[col * CS_PO_STRIDE + (z * 8 + y) * 8 + x] = fmaxf(fmaf(lo[m][0][r], 1.0f / CS_LO, hi[m][0][r]), a.floor);
+                        e[col * CS_PO_STRIDE + (z * 8 + y) * 8 + x] = rf_max(fmaf(lo[m][0][r], 1.0f / CS_LO, hi[m][0][r]), a.floor);
                     }
             }
             __syncthreads();
@@ -596,7 +596,7 @@ __global__ __launch_bounds__(512, 4) void k_conv3_cin1_presplit(Cin1PreArgs a) {
 #pragma unroll
     for (int z = 0; z < 8; ++z)
 #pragma unroll
-        for (int co = 0; co < 8; ++co) act[z][co] = fmaxf(acc2[z][co >> 1][co & 1], 0.f);
+        for (int co = 0; co < 8; ++co) act[z][co] = rf_relu(acc2[z][co >> 1][co & 1]);
     {   // statistics of the sample: per (wave, cout) float64 sums by recursive halving, then the 8 waves in order
         double v[16];
 #pragma unroll
@@ -655,8 +655,8 @@ __global__ __launch_bounds__(512, 4) void k_conv3_cin1_presplit(Cin1PreArgs a) {
         for (int cp = 0; cp < 4; ++cp) {
             const f32x2 relu = (f32x2){act[z][2 * cp], act[z][2 * cp + 1]};
             f32x2 v = __builtin_elementwise_fma(relu + negc[cp], sc[cp], sh[cp]);
-            v[0] = __builtin_amdgcn_fmed3f(v[0], -65504.f, 65504.f);
-            v[1] = __builtin_amdgcn_fmed3f(v[1], -65504.f, 65504.f);
+            v[0] = rf_clamp_f16(v[0]);
+            v[1] = rf_clamp_f16(v[1]);
             const h2 hh = __builtin_convertvector(v, h2);
             const f32x2 back = __builtin_convertvector(hh, f32x2);
             const h2 ll = __builtin_convertvector((v - back) * CS_LO, h2);      // v - h is exact in fp32

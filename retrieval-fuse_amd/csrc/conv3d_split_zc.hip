@@ -186,26 +186,26 @@ __global__ __launch_bounds__(512, 4) void k_conv3_split_zc(ConvArgs a, SplitPreO
                 for (int m = 0; m < 4; ++m) {
                     const f32x4 v = acc[m];
                     *reinterpret_cast<float4*>(o + (size_t)(z0 + 4 * zh + m) * E * E) =
-                        make_float4(fmaxf(v[0], a.floor), fmaxf(v[1], a.floor), fmaxf(v[2], a.floor), fmaxf(v[3], a.floor));
+                        make_float4(rf_max(v[0], a.floor), rf_max(v[1], a.floor), rf_max(v[2], a.floor), rf_max(v[3], a.floor));
                 }
             }
             if (a.stats) {
 #pragma unroll
                 for (int m = 0; m < 4; ++m)
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) { const double v = (double)fmaxf(acc[m][r], 0.f); fsm += v; fsq += v * v; }
+                    for (int r = 0; r < 4; ++r) { const double v = (double)rf_relu(acc[m][r]); fsm += v; fsq += v * v; }
             }
         }
         if (want_pool) {                                              // z pair = planes (2 zp, 2 zp + 1), x pairs in r, y pair in lane ^ 32
 #pragma unroll
             for (int zp = 0; zp < 2; ++zp) {
                 const f32x4 u = acc[2 * zp], v = acc[2 * zp + 1];
-                float p0 = fmaxf(fmaxf(u[0], u[1]), fmaxf(v[0], v[1]));
-                float p1 = fmaxf(fmaxf(u[2], u[3]), fmaxf(v[2], v[3]));
-                p0 = fmaxf(p0, __shfl_xor(p0, 32, 64));
-                p1 = fmaxf(p1, __shfl_xor(p1, 32, 64));
-                p0 = fmaxf(p0, 0.f);                                  // max and ReLU commute
-                p1 = fmaxf(p1, 0.f);
+                float p0 = rf_max(rf_max(u[0], u[1]), rf_max(v[0], v[1]));
+                float p1 = rf_max(rf_max(u[2], u[3]), rf_max(v[2], v[3]));
+                p0 = rf_max(p0, __shfl_xor(p0, 32, 64));
+                p1 = rf_max(p1, __shfl_xor(p1, 32, 64));
+                p0 = rf_relu(p0);                                  // max and ReLU commute
+                p1 = rf_relu(p1);
                 pooled[zp] = make_float2(p0, p1);
                 if (kq < 2) { psm += (double)p0 + (double)p1; psq += (double)p0 * (double)p0 + (double)p1 * (double)p1; }
             }
@@ -545,7 +545,7 @@ __global__ __launch_bounds__(512, 4) void k_conv3_split_zcm(ConvArgs a, SplitPre
 #pragma unroll
                 for (int m = 0; m < 4; ++m)
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) hi[m][r] = fmaxf(fmaf(lo[m][r], 1.0f / CS_LO, hi[m][r]), a.floor);      // the box's output values
+                    for (int r = 0; r < 4; ++r) hi[m][r] = rf_max(fmaf(lo[m][r], 1.0f / CS_LO, hi[m][r]), a.floor);      // the box's output values
             }
             if (EPI == 0 && last) {
                 // outputs straight from the accumulators: D tile col = lane & 15 = cout, rows 4 (lane >> 4) + r = voxel x = i & 7, y = 2 yq + (i >> 3).
@@ -565,7 +565,7 @@ __global__ __launch_bounds__(512, 4) void k_conv3_split_zcm(ConvArgs a, SplitPre
 #pragma unroll
                         for (int m = 0; m < 4; ++m)
 #pragma unroll
-                            for (int r = 0; r < 4; ++r) { const double v = (double)fmaxf(hi[m][r], 0.f); fsm += v; fsq += v * v; }
+                            for (int r = 0; r < 4; ++r) { const double v = (double)rf_relu(hi[m][r]); fsm += v; fsq += v * v; }
                     }
                 }
                 if (a.pool_mode) {                                    // fused MaxPool3d(2): z pair = planes (2 zp, 2 zp + 1), x pairs in r, y pair in lane ^ 32
@@ -573,12 +573,12 @@ __global__ __launch_bounds__(512, 4) void k_conv3_split_zcm(ConvArgs a, SplitPre
 #pragma unroll
                     for (int zp = 0; zp < 2; ++zp) {
                         const f32x4 u = hi[2 * zp], v = hi[2 * zp + 1];
-                        float p0 = fmaxf(fmaxf(u[0], u[1]), fmaxf(v[0], v[1]));
-                        float p1 = fmaxf(fmaxf(u[2], u[3]), fmaxf(v[2], v[3]));
-                        p0 = fmaxf(p0, __shfl_xor(p0, 32, 64));
-                        p1 = fmaxf(p1, __shfl_xor(p1, 32, 64));
-                        p0 = fmaxf(p0, 0.f);                          // max and ReLU commute
-                        p1 = fmaxf(p1, 0.f);
+                        float p0 = rf_max(rf_max(u[0], u[1]), rf_max(v[0], v[1]));
+                        float p1 = rf_max(rf_max(u[2], u[3]), rf_max(v[2], v[3]));
+                        p0 = rf_max(p0, __shfl_xor(p0, 32, 64));
+                        p1 = rf_max(p1, __shfl_xor(p1, 32, 64));
+                        p0 = rf_relu(p0);                          // max and ReLU commute
+                        p1 = rf_relu(p1);
                         if (kq < 2) {
                             psm += (double)p0 + (double)p1;
                             psq += (double)p0 * (double)p0 + (double)p1 * (double)p1;

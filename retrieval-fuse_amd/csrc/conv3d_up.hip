@@ -800,7 +800,7 @@ __global__ __launch_bounds__(512, 4) void k_conv3_up(UpArgs a) {
                 int X, Y, Z, s;
             up_lattice<TE>(v, s, Z, Y, X);
                 const int lin = s * TE3 + ((2 * Z + pz) * TE + (2 * Y + py)) * TE + (2 * X + px);
-                eb[li * (P + 1) + lin] = fmaxf(acc[mb][nb][r], 0.f);
+                eb[li * (P + 1) + lin] = rf_relu(acc[mb][nb][r]);
             }
         }
         __syncthreads();
@@ -826,7 +826,7 @@ __global__ __launch_bounds__(512, 4) void k_conv3_up(UpArgs a) {
                 for (int mb = 0; mb < MB; ++mb)
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
-                        const double v = (double)fmaxf(acc[mb][nb][r], 0.f);
+                        const double v = (double)rf_relu(acc[mb][nb][r]);
                         sm += v; sq += v * v;
                     }
                 sm += __shfl_xor(sm, 16, 64); sq += __shfl_xor(sq, 16, 64);
@@ -839,7 +839,7 @@ __global__ __launch_bounds__(512, 4) void k_conv3_up(UpArgs a) {
                 for (int mb = 0; mb < MB; ++mb)
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
-                        const double v = (double)fmaxf(acc[mb][nb][r], 0.f);
+                        const double v = (double)rf_relu(acc[mb][nb][r]);
                         sm += v; sq += v * v;
                     }
                 red[((wave * SPW + kq) * 16 + li) * 2] = sm;
@@ -873,7 +873,7 @@ __global__ __launch_bounds__(512, 4) void k_conv3_up(UpArgs a) {
                 int X, Y, Z, s;
                 up_lattice<TE>(v, s, Z, Y, X);
                 const int lin = ((2 * Z + pz) * TE + (2 * Y + py)) * TE + (2 * X + px);
-                eb[(4 * h + j4) * (P + 1) + lin] = fmaxf(acc4[h][i], 0.f);
+                eb[(4 * h + j4) * (P + 1) + lin] = rf_relu(acc4[h][i]);
             }
         __syncthreads();
         for (int q = tid_e; q < 8 * (P / 4); q += NT) {
@@ -894,7 +894,7 @@ __global__ __launch_bounds__(512, 4) void k_conv3_up(UpArgs a) {
                 double sm = 0.0, sq = 0.0;
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    const double v = (double)fmaxf(acc4[h][i], 0.f);
+                    const double v = (double)rf_relu(acc4[h][i]);
                     sm += v; sq += v * v;
                 }
 #pragma unroll

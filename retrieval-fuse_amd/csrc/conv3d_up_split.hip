@@ -146,7 +146,7 @@ struct UpSplitArgs {
 __device__ __forceinline__ void us_split8(const float (&y)[8], h8& h, h8& l) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-        const float v = __builtin_amdgcn_fmed3f(y[j] * US_ACT_SCALE, -65504.f, 65504.f);
+        const float v = rf_clamp_f16(y[j] * US_ACT_SCALE);
         const _Float16 hh = (_Float16)v;
         h[j] = hh;
         l[j] = (_Float16)fmaf(-US_LO, (float)hh, v * US_LO);          // (v - h) * 2^11: exact either way, one v_fma_mix instead of cvt + sub + mul
@@ -157,7 +157,7 @@ __device__ __forceinline__ void us_split8(const float (&y)[8], h8& h, h8& l) {
 __device__ __forceinline__ void us_split8_scaled(const float (&y)[8], h8& h, h8& l) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-        const float v = __builtin_amdgcn_fmed3f(y[j], -65504.f, 65504.f);
+        const float v = rf_clamp_f16(y[j]);
         const _Float16 hh = (_Float16)v;
         h[j] = hh;
         l[j] = (_Float16)fmaf(-US_LO, (float)hh, v * US_LO);
@@ -398,7 +398,7 @@ __global__ __launch_bounds__(512, 2) void k_conv3_up_split(UpSplitArgs a) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int lin = (2 * m + pz) * 64 + (2 * yj + py) * 8 + 2 * r + px;
-                    e[(nb * 16 + col) * US_T_STRIDE + lin] = fmaxf(fmaf(lo[m][nb][r], 1.0f / US_LO, hi[m][nb][r]), 0.f);
+                    e[(nb * 16 + col) * US_T_STRIDE + lin] = rf_relu(fmaf(lo[m][nb][r], 1.0f / US_LO, hi[m][nb][r]));
                 }
     }
     __syncthreads();
@@ -878,7 +878,7 @@ __global__ __launch_bounds__(512, 2) void k_conv3_up_split_pp(UpSplitArgs a) {
 #pragma unroll
             for (int j = 0; j < 2; ++j)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) hi[vb][j][r] = fmaxf(fmaf(lo[vb][j][r], 1.0f / US_LO, hi[vb][j][r]), 0.f);
+                for (int r = 0; r < 4; ++r) hi[vb][j][r] = rf_relu(fmaf(lo[vb][j][r], 1.0f / US_LO, hi[vb][j][r]));
         double2* chst = reinterpret_cast<double2*>(lds + PP_CHST);
         double2* chs = reinterpret_cast<double2*>(lds + PP_CHS);
         float4* trip = reinterpret_cast<float4*>(lds + PP_TRIP);
@@ -1167,7 +1167,7 @@ __global__ __launch_bounds__(512, NB >= 3 ? 2 : 4) void k_conv3_up_split_s4(UpSp
                     const int row = 4 * g + r, sm = 4 * (m >> 1) + (row >> 2);
                     const int z = m & 1 ? 2 - pz : 3 * pz;
                     const int lin = sm * 64 + z * 16 + (2 * ((row >> 1) & 1) + py) * 4 + 2 * (row & 1) + px;
-                    e[(nb * 16 + col) * U4_E_STRIDE + lin] = fmaxf(fmaf(lo[m][nb][r], 1.0f / US_LO, hi[m][nb][r]), 0.f);
+                    e[(nb * 16 + col) * U4_E_STRIDE + lin] = rf_relu(fmaf(lo[m][nb][r], 1.0f / US_LO, hi[m][nb][r]));
                 }
     }
     __syncthreads();
@@ -1288,7 +1288,7 @@ __global__ __launch_bounds__(512, 4) void k_conv3_up_split_box(UpSplitArgs a, in
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int lin = (2 * m + pz) * 64 + (2 * yj + py) * 8 + 2 * r + px;
-                    e[(nb * 16 + col) * UB_E_STRIDE + lin] = fmaxf(fmaf(lo[m][nb][r], 1.0f / US_LO, hi[m][nb][r]), 0.f);
+                    e[(nb * 16 + col) * UB_E_STRIDE + lin] = rf_relu(fmaf(lo[m][nb][r], 1.0f / US_LO, hi[m][nb][r]));
                 }
     }
     __syncthreads();
@@ -1453,7 +1453,7 @@ __global__ __launch_bounds__(512, 4) void k_conv3_up_split_boxp(UpSplitArgs a, i
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int lin = (2 * m + pz) * 64 + (2 * yj + py) * 8 + 2 * r + px;
-                    e[col * UB_E_STRIDE + lin] = fmaxf(fmaf(lo[m][0][r], 1.0f / US_LO, hi[m][0][r]), 0.f);
+                    e[col * UB_E_STRIDE + lin] = rf_relu(fmaf(lo[m][0][r], 1.0f / US_LO, hi[m][0][r]));
                 }
         }
         if (b + bs < b1) stage(cur ^ 1);
@@ -1665,7 +1665,7 @@ __global__ __launch_bounds__(512, 2) void k_conv3_up_split_boxskip(UpSplitArgs a
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int lin = (2 * m + pz) * 64 + (2 * yj + py) * 8 + 2 * r + px;
-                    e[(nb * 16 + col) * UB_E_STRIDE + lin] = fmaxf(fmaf(lo[m][nb][r], 1.0f / US_LO, hi[m][nb][r]), 0.f);
+                    e[(nb * 16 + col) * UB_E_STRIDE + lin] = rf_relu(fmaf(lo[m][nb][r], 1.0f / US_LO, hi[m][nb][r]));
                 }
     }
     __syncthreads();

@@ -84,7 +84,7 @@ __device__ __forceinline__ void conv_box_epilogue(const ConvArgs& a, f32x4 (&acc
                 const int co = cob + nb * 16 + (lane & 15);
                 if (co < a.cout) {
                     f32x4 v = acc[mb][nb];
-                    float4 o = make_float4(fmaxf(v[0], a.floor), fmaxf(v[1], a.floor), fmaxf(v[2], a.floor), fmaxf(v[3], a.floor));
+                    float4 o = make_float4(rf_max(v[0], a.floor), rf_max(v[1], a.floor), rf_max(v[2], a.floor), rf_max(v[3], a.floor));
                     *reinterpret_cast<float4*>(a.out + ((size_t)nn * a.cout + co) * vol + off) = o;
                 }
             }
@@ -108,7 +108,7 @@ __device__ __forceinline__ void conv_box_epilogue(const ConvArgs& a, f32x4 (&acc
                 for (int mb = 0; mb < MB; ++mb)
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
-                        const double v = (double)fmaxf(acc[mb][nb][r], 0.f);
+                        const double v = (double)rf_relu(acc[mb][nb][r]);
                         sm += v; sq += v * v;
                     }
                 sm += __shfl_xor(sm, 16, 64); sq += __shfl_xor(sq, 16, 64);
@@ -123,7 +123,7 @@ __device__ __forceinline__ void conv_box_epilogue(const ConvArgs& a, f32x4 (&acc
                     double sm = 0.0, sq = 0.0;
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
-                        const double v = (double)fmaxf(acc[mb][nb][r], 0.f);
+                        const double v = (double)rf_relu(acc[mb][nb][r]);
                         sm += v; sq += v * v;
                     }
                     sm += __shfl_xor(sm, 16, 64); sq += __shfl_xor(sq, 16, 64);      // lanes {0..31}: sample 2mb, {32..63}: 2mb+1
@@ -174,12 +174,12 @@ __device__ __forceinline__ void conv_box_epilogue(const ConvArgs& a, f32x4 (&acc
 #pragma unroll
                 for (int yh = 0; yh < 2; ++yh) {
                     const f32x4 u = acc[2 * yh][nb], v = acc[2 * yh + 1][nb];
-                    float p0 = fmaxf(fmaxf(u[0], u[1]), fmaxf(v[0], v[1]));
-                    float p1 = fmaxf(fmaxf(u[2], u[3]), fmaxf(v[2], v[3]));
-                    p0 = fmaxf(p0, __shfl_xor(p0, 32, 64));
-                    p1 = fmaxf(p1, __shfl_xor(p1, 32, 64));
-                    p0 = fmaxf(p0, 0.f);                        // max and ReLU commute
-                    p1 = fmaxf(p1, 0.f);
+                    float p0 = rf_max(rf_max(u[0], u[1]), rf_max(v[0], v[1]));
+                    float p1 = rf_max(rf_max(u[2], u[3]), rf_max(v[2], v[3]));
+                    p0 = rf_max(p0, __shfl_xor(p0, 32, 64));
+                    p1 = rf_max(p1, __shfl_xor(p1, 32, 64));
+                    p0 = rf_relu(p0);                        // max and ReLU commute
+                    p1 = rf_relu(p1);
                     if (kq < 2) {
                         sm += (double)p0 + (double)p1;
                         sq += (double)p0 * (double)p0 + (double)p1 * (double)p1;

@@ -23,7 +23,7 @@ constexpr bool CS_S4_WIDE = true;
 __device__ __forceinline__ void cs_split8(const float (&y)[8], h8& h, h8& l) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-        const float v = __builtin_amdgcn_fmed3f(y[j] * CS_ACT_SCALE, -65504.f, 65504.f);
+        const float v = rf_clamp_f16(y[j] * CS_ACT_SCALE);
         const _Float16 hh = (_Float16)v;
         h[j] = hh;
         l[j] = (_Float16)fmaf(-CS_LO, (float)hh, v * CS_LO);          // (v - h) * 2^11: exact either way, one v_fma_mix instead of cvt + sub + mul

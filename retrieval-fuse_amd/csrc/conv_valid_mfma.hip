@@ -541,7 +541,7 @@ __device__ __forceinline__ void convv_store_split(unsigned char* o, size_t plane
     rf_h4 hh, ll;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-        const float t = __builtin_amdgcn_fmed3f(v[e] * (1.0f / 16), -65504.f, 65504.f);
+        const float t = rf_clamp_f16(v[e] * (1.0f / 16));
         const _Float16 h = (_Float16)t;
         hh[e] = h;
         ll[e] = (_Float16)fmaf(-2048.0f, (float)h, t * 2048.0f);

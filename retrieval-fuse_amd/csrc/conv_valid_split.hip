@@ -306,7 +306,7 @@ __global__ __launch_bounds__(VS_NT, WPE) void k_convv_split(ConvVSArgs a) {
                             h4 hh, ll;
 #pragma unroll
                             for (int e = 0; e < 4; ++e) {
-                                const float t = __builtin_amdgcn_fmed3f(v[b][e] * sc, -65504.f, 65504.f);
+                                const float t = rf_clamp_f16(v[b][e] * sc);
                                 const _Float16 h = (_Float16)t;
                                 hh[e] = h;
                                 ll[e] = (_Float16)fmaf(-VS_LO, (float)h, t * VS_LO);     // (t - h) * 2^11, exact either way; one v_fma_mix_f32
@@ -397,7 +397,7 @@ __global__ __launch_bounds__(VS_NT, WPE) void k_convv_split(ConvVSArgs a) {
                         h4 hh, ll;
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
-                            const float t = __builtin_amdgcn_fmed3f(eb[(wave * 4 + e) * VS_EV + lane + 64 * i] * VS_ACT_SCALE, -65504.f, 65504.f);
+                            const float t = rf_clamp_f16(eb[(wave * 4 + e) * VS_EV + lane + 64 * i] * VS_ACT_SCALE);
                             const _Float16 h = (_Float16)t;
                             hh[e] = h;
                             ll[e] = (_Float16)fmaf(-VS_LO, (float)h, t * VS_LO);

@@ -401,8 +401,8 @@ __global__ __launch_bounds__(PG_NT, 1) void k_convv_split_pg(ConvPGArgs a) {
                             const f32x2 t0 = __builtin_elementwise_fma(l2, (f32x2){PG_ACT_SCALE / PG_LO, PG_ACT_SCALE / PG_LO}, h2 * (f32x2){PG_ACT_SCALE, PG_ACT_SCALE}) + b2;
                             const f32x2 ts = t0 * (f32x2){a.slope, a.slope};
                             f32x2 t;
-                            t.x = __builtin_amdgcn_fmed3f(fmaxf(t0.x, ts.x), -65504.f, 65504.f);
-                            t.y = __builtin_amdgcn_fmed3f(fmaxf(t0.y, ts.y), -65504.f, 65504.f);
+                            t.x = rf_clamp_f16(rf_max(t0.x, ts.x));
+                            t.y = rf_clamp_f16(rf_max(t0.y, ts.y));
                             const f32x2 tl = t * (f32x2){PG_LO, PG_LO};
                             const _Float16 ha = (_Float16)t.x, hb = (_Float16)t.y;
                             hh[r] = ha; hh[r + 1] = hb;

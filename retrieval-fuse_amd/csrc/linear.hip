@@ -107,7 +107,7 @@ __global__ __launch_bounds__(256, 2) void k_linear_mfma(const float* __restrict_
                 const int row = row0 + wave * 32 + mb * 16 + (lane >> 4) * 4 + r;
                 if (row < rows) {
                     float v = acc[mb][nb][r] + bv;
-                    if (act == RF_ACT_RELU) v = fmaxf(v, 0.f);
+                    if (act == RF_ACT_RELU) v = rf_relu(v);
                     else if (act == RF_ACT_LEAKY) v = v > 0.f ? v : v * slope;
                     y[(size_t)row * nout + co] = v;
                 }
@@ -252,7 +252,7 @@ __global__ __launch_bounds__(256) void k_l2norm_rows(float* __restrict__ x, int 
         float s = 0.f;
         for (int j = lane; j < dim; j += 64) s += p[j] * p[j];
         s = wave_sum(s);
-        const float denom = fmaxf(sqrtf(s), eps);
+        const float denom = rf_max(sqrtf(s), eps);
         for (int j = lane; j < dim; j += 64) p[j] = p[j] / denom;
     }
 }

@@ -366,7 +366,7 @@ def _abs_max(t):
 
 def split_range_ok(weight, gamma=None, beta=None, group_elements=0):
     """True when the split-operand forms cannot saturate for this layer, whatever the input (see SPLIT_MAX_ABS_* above)."""
-    w_ok = _abs_max(weight) <= SPLIT_MAX_ABS_WEIGHT                      # NaN / inf weights compare False: fp32 path, like the reference
+    w_ok = _abs_max(weight) <= SPLIT_MAX_ABS_WEIGHT                      # NaN / inf weights compare False: fp32 path, which carries them like the reference
     if gamma is None:
         return w_ok
     return w_ok and _abs_max(gamma) * (float(group_elements) ** 0.5) + _abs_max(beta) <= SPLIT_MAX_ABS_ACT
