@@ -329,6 +329,25 @@ size_t rf_conv3d_k3_wgrad_split_ws_bytes(int cin, int cout, int n, int edge);
 int rf_conv3d_k3_wgrad_split(const float* x, int cin, int n, int edge, const float* gn_affine, const float* dz, int cout, const float* scales,
                              float* dw, void* ws, size_t ws_bytes, void* stream);
 
+/* Backward of the patch encoders' valid strided conv + bias + LeakyReLU (rf_conv3d_valid_leaky*; reference model/retrieval.py:4-361, trained by
+ * trainer/train_retrieval.py), csrc/conv_valid_backward.hip.  Every sum in a fixed order (no atomics): repeated calls give the same bits.
+ *   rf_conv3d_valid_leaky_backward   dz = y > 0 ? dy : slope * dy from the saved output y [n][cout][so^3] (torch's rule for the reference's in-place
+ *                                    LeakyReLU) and db[co] = sum dz (fp32 partials per workgroup, float64 across them).  ws: *_ws_bytes(n, cout, so).
+ *   rf_conv3d_valid_dgrad            dx[n][ci][p] = sum_{co, t : p = o * stride + t} dz[n][co][o] * W[co][ci][t], input edge s, so = (s - k) / stride + 1,
+ *                                    k <= 5, stride 1 or 2: an implicit GEMM per parity phase on the fp32 matrix cores (stride 2, k = 3: 8/4/4/4/2/2/2/1
+ *                                    taps, no inserted zeros); planes no output reads come out as 0.  wd_packed: W OIDHW as [k^3][cout -> 4][cin -> 16]
+ *                                    (zero padded, rf_convv_dgrad_packed_floats floats; rfuse/ops.py packs it).
+ *   rf_conv3d_valid_wgrad            dw[co][ci][t] = sum_{n, o} dz[n][co][o] * x[n][ci][o * stride + t] (OIDHW) on the fp32 matrix cores, K = n * so^3 cut
+ *                                    into fixed slices of 256 output rows, fp32 partials per slice summed in float64.  ws: *_ws_bytes(n, cin, cout, so, k). */
+size_t rf_conv3d_valid_leaky_backward_ws_bytes(int n, int cout, int so);
+int rf_conv3d_valid_leaky_backward(const float* dy, const float* y, int n, int cout, int so, float slope, float* dz, float* db, void* ws,
+                                   size_t ws_bytes, void* stream);
+size_t rf_convv_dgrad_packed_floats(int cout, int cin, int k);
+int rf_conv3d_valid_dgrad(const float* dz, int n, int cout, int so, const float* wd_packed, int cin, int k, int stride, int s, float* dx, void* stream);
+size_t rf_conv3d_valid_wgrad_ws_bytes(int n, int cin, int cout, int so, int k);
+int rf_conv3d_valid_wgrad(const float* x, int n, int cin, int s, const float* dz, int cout, int k, int stride, float* dw, void* ws, size_t ws_bytes,
+                          void* stream);
+
 /* --------------------------------------------------------------------------------------------- fold / unfold */
 
 /* Unfold3D.forward (model/attention.py:186-188): x [b][c][s^3] -> rows [(b*r^3)][c][e^3], r = s/e, row = ((b*r+px)*r+py)*r+pz */

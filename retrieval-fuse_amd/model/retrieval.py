@@ -14,13 +14,17 @@ so ``model.get_retrieval_networks`` (reference model/__init__.py:6-38) keeps wor
 
 The two BatchNorm variants (PatchNorm08 :160-184, PatchNorm32 :31-61) construct and serialise identically but their
 forward is not built: no shipped config selects them.
+
+Training (the reference's trainer/train_retrieval.py: both encoders in grad mode, NT-Xent, Adam): when the input or a parameter needs a gradient,
+``forward`` runs every layer through rfuse/autograd.py -- ConvValidLeaky for the convs (the inference kernels forward, HIP backward kernels), Linear
+for the MLP layers and final_layer.  ``forward_grid`` and the BatchNorm variants stay inference-only and raise in grad mode.
 """
 import torch
 from torch import nn
 
 from model.attention import LinearParams, ActivationMarker
 from model.unet import Conv3dParams
-from rfuse import ops
+from rfuse import autograd, ops
 
 
 class _MLPPatchEncoder(nn.Module):
@@ -37,11 +41,21 @@ class _MLPPatchEncoder(nn.Module):
         self.layers = nn.ModuleList(layers)
 
     def forward(self, x):
+        if ops.needs_grad(x, *self.parameters()):
+            return self._forward_autograd(x)
         ops._no_grad_only(x, self.layers[0].weight)
         x = x.contiguous().reshape([x.shape[0], -1])
         last = len(self.layers) - 1
         for i in range(0, len(self.layers), 2):
             x = self.layers[i].apply_to(x, ops.ACT_NONE if i == last else ops.ACT_RELU)
+        return x.reshape([x.shape[0], x.shape[1], 1, 1, 1])
+
+    def _forward_autograd(self, x):
+        x = x.contiguous().reshape([x.shape[0], -1])
+        last = len(self.layers) - 1
+        for i in range(0, len(self.layers), 2):
+            layer = self.layers[i]
+            x = autograd.Linear.apply(x, layer.weight, layer.bias, ops.ACT_NONE if i == last else ops.ACT_RELU, 0.0)
         return x.reshape([x.shape[0], x.shape[1], 1, 1, 1])
 
 
@@ -139,8 +153,21 @@ class _ConvPatchEncoder(nn.Module):
     def forward(self, x):
         if self.BATCHNORM:
             raise NotImplementedError(f'{type(self).__name__}: BatchNorm patch encoders are not built (no shipped config selects them)')
+        if ops.needs_grad(x, *self.parameters()):
+            return self._forward_autograd(x)
         ops._no_grad_only(x, self.final_layer.weight)
         return self._head(self._run([layer for layer in self.layers if isinstance(layer, Conv3dParams)], x.contiguous()))
+
+    def _forward_autograd(self, x):
+        """grad mode: one ConvValidLeaky per conv layer (fp32 activations between layers), final_layer through autograd.Linear"""
+        x = x.contiguous()
+        for layer in self.layers:
+            if isinstance(layer, Conv3dParams):
+                x = autograd.ConvValidLeaky.apply(x, layer.weight, layer.bias, layer, self, 0.2)
+        if tuple(x.shape[2:]) != (1, 1, 1):
+            raise ValueError(f'{type(self).__name__}: input window does not reduce to 1^3 (got {tuple(x.shape[2:])})')
+        x = autograd.Linear.apply(x.reshape(x.shape[0], x.shape[1]), self.final_layer.weight, self.final_layer.bias, ops.ACT_NONE, 0.0)
+        return x.reshape([x.shape[0], x.shape[1], 1, 1, 1])
 
     def grid_plan(self, window, step, npatch):
         """How many leading conv layers to evaluate on the whole grid of npatch^3 windows (edge `window`, stride `step`) instead of per window:

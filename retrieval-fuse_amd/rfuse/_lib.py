@@ -110,6 +110,12 @@ SIGNATURES = {
     'rf_conv3d_k3_wgrad_split_supported': (c_i, [c_i, c_i, c_i, c_i]),
     'rf_conv3d_k3_wgrad_split_ws_bytes': (c_sz, [c_i, c_i, c_i, c_i]),
     'rf_conv3d_k3_wgrad_split': (c_i, [c_fp, c_i, c_i, c_i, c_fp, c_fp, c_i, c_fp, c_fp, c_p, c_sz, c_p]),
+    'rf_conv3d_valid_leaky_backward_ws_bytes': (c_sz, [c_i, c_i, c_i]),
+    'rf_conv3d_valid_leaky_backward': (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_f, c_fp, c_fp, c_p, c_sz, c_p]),
+    'rf_convv_dgrad_packed_floats': (c_sz, [c_i, c_i, c_i]),
+    'rf_conv3d_valid_dgrad': (c_i, [c_fp, c_i, c_i, c_i, c_fp, c_i, c_i, c_i, c_i, c_fp, c_p]),
+    'rf_conv3d_valid_wgrad_ws_bytes': (c_sz, [c_i, c_i, c_i, c_i, c_i]),
+    'rf_conv3d_valid_wgrad': (c_i, [c_fp, c_i, c_i, c_i, c_fp, c_i, c_i, c_i, c_fp, c_p, c_sz, c_p]),
     'rf_unfold3d': (c_i, [c_fp, c_i, c_i, c_i, c_i, c_fp, c_p]),
     'rf_fold3d': (c_i, [c_fp, c_i, c_i, c_i, c_i, c_fp, c_p]),
     'rf_linear_pack_weight': (c_i, [c_fp, c_i, c_i, c_fp, c_p]),

@@ -14,6 +14,14 @@ retrieval_backbone / attention parameters, :295-306 phase hand-over).  Built her
   Linear       y = act(x W^T + b)               the layers of AttentionFeatureEncoder (reference model/attention.py:29-46)
       backward  dx = rf_linear(dpre, W^T-as-weight),  dW = rf_linear_wgrad(dpre, x) in row chunks summed in float64
   MaxPool3d(2) / nearest x2 upsample             rf_maxpool3d_2 + rf_maxpool3d_2_backward, rf_upsample3d_2 + rf_sumpool3d_2 (bit-equal to torch's)
+  ConvValidLeaky  y = LeakyReLU(conv_valid(x, W, stride) + b)   one layer of the conv patch encoders (reference model/retrieval.py:4-361), trained
+                with NT-Xent by trainer/train_retrieval.py
+      forward   the inference kernels, chosen per layer like model/retrieval.py:_ConvPatchEncoder._conv chooses them, with an fp32 output (no split
+                hand-over between layers in grad mode)
+      backward  rf_conv3d_valid_leaky_backward (dz from the saved output, db in float64) -> rf_conv3d_valid_dgrad (fp32 MFMA per parity phase; skipped
+                when x needs no gradient: the first layer's input is data) and rf_conv3d_valid_wgrad (fp32 MFMA, split K, float64 slice sum).  fp32
+                operands throughout, so NT-Xent's small gradients (1e-3 ... 1e-7) need no rescaling.
+                The MLP patch encoders (Patch04 / Patch05 / Patch04V2) and every encoder's final_layer run through Linear below.
 
 torch does the bookkeeping and the light per-row work: transposes / flips of weights, the activation mask of Linear, sums over the batch of
 per-sample float64 pieces, the 16 -> 1 pointwise conv + tanh of the final decoder, fold / unfold as views, and the patch attention's per-row
@@ -21,7 +29,8 @@ normalise / scores / softmax or straight-through Gumbel-hard / blend (model/atte
 that the whole training graph of the reference (trainer/train_refinement.py:108-116 forward_full, all four networks trainable = phase 3) runs
 through the drop-in modules in grad mode; loss and every parameter gradient are checked against float64 autograd of the oracle in
 tests/test_autograd_gpu.py.  Not built: backward of the pre-split pair routes and the fused attention MLP (grad mode takes the plain routes), the
-patch encoders (trained by trainer/train_retrieval.py, outside the refinement path).
+BatchNorm patch encoders (PatchNorm08 / PatchNorm32: no shipped config selects them) and the patch encoders' forward_grid (the database build and
+the queries never train).
 """
 import torch
 import torch.nn.functional as F
@@ -216,6 +225,31 @@ class Linear(torch.autograd.Function):
             dw = ops.linear_wgrad(dpre, x)
             db = dpre.double().sum(0).float() if ctx.has_bias else None
         return dx, dw, db, None, None
+
+
+class ConvValidLeaky(torch.autograd.Function):
+    """one layer of a conv patch encoder; ``layer`` (a model.unet.Conv3dParams holding weight / bias) and ``encoder`` (its _ConvPatchEncoder) pick the
+    forward kernel and hold the cached weight images, no gradient flows to them"""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, layer, encoder, slope):
+        x = x.contiguous()
+        with torch.no_grad():
+            y = encoder._conv(layer, x)
+        ctx.save_for_backward(x, weight, y)
+        ctx.k, ctx.stride, ctx.slope = layer.kernel_size, layer.stride, slope
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight, y = ctx.saved_tensors
+        with torch.no_grad():
+            dz, db = ops.conv3d_valid_leaky_backward(dy.contiguous(), y, ctx.slope)
+            dx = None
+            if ctx.needs_input_grad[0]:
+                dx = ops.conv3d_valid_dgrad(dz, ops.pack_convv_dgrad_weight(weight), x.shape[1], ctx.k, ctx.stride, x.shape[2])
+            dw = ops.conv3d_valid_wgrad(x, dz, ctx.k, ctx.stride) if ctx.needs_input_grad[1] else None
+        return dx, dw, db if ctx.needs_input_grad[2] else None, None, None, None
 
 
 @ops._device_scoped

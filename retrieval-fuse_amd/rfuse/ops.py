@@ -66,8 +66,8 @@ def needs_grad(*tensors):
 def _no_grad_only(*tensors):
     if needs_grad(*tensors):
         raise NotImplementedError(
-            'this rfuse op implements inference only; call under torch.no_grad().  Backward exists for the SingleConv layers and '
-            'the attention feature encoders (rfuse/autograd.py, SURVEY.md section 8f row N4), not for this op')
+            'this rfuse op implements inference only; call under torch.no_grad().  Backward exists for the SingleConv layers, '
+            'the attention feature encoders and the patch encoders\' forward (rfuse/autograd.py, SURVEY.md section 8f row N4), not for this op')
 
 
 _ws_cache = {}
@@ -96,7 +96,7 @@ class PackedWeight:
         key = (w.data_ptr(), w._version, tuple(w.shape), w.device) + extra
         if key != self._key:
             self._packed = {'conv3': pack_conv3_weight, 'linear': pack_linear_weight, 'convv': pack_convv_weight,
-                            'convvl': pack_convv_lds_weight, 'convvv': pack_convv_valu_weight, 'conv3up': pack_conv3_up_weight, 'conv3ups': pack_conv3_up_split_weight, 'conv3s': pack_conv3_split_weight, 'conv3e2': pack_conv3_e2_split_weight, 'convvs': pack_convv_split_weight, 'convvpg': pack_convv_split_pg_weight}[self.kind](w, *extra)
+                            'convvl': pack_convv_lds_weight, 'convvv': pack_convv_valu_weight, 'conv3up': pack_conv3_up_weight, 'conv3ups': pack_conv3_up_split_weight, 'conv3s': pack_conv3_split_weight, 'conv3e2': pack_conv3_e2_split_weight, 'convvs': pack_convv_split_weight, 'convvpg': pack_convv_split_pg_weight, 'convvd': pack_convv_dgrad_weight}[self.kind](w, *extra)
             self._key = key
             self._ready.packed_on(w.device)
         else:
@@ -957,6 +957,60 @@ def conv3d_valid_leaky(x, w, bias, stride, slope):
     _lib.check(_lib.load().rf_conv3d_valid_leaky(_p(x), n, cin, s, _p(w.detach()), _p(bias.detach() if bias is not None else None), cout, k,
                                                  stride, slope, _p(out), _stream()), 'rf_conv3d_valid_leaky')
     return out
+
+
+# ------------------------------------------------------------------------------------- valid conv backward (patch encoders)
+
+@_device_scoped
+def conv3d_valid_leaky_backward(dy, y, slope):
+    """dz = y > 0 ? dy : slope * dy from the saved output y, and db = sum of dz over samples and voxels (float64 across workgroups) -> (dz, db)"""
+    _req(dy, 'dy'), _req(y, 'y')
+    if dy.shape != y.shape:
+        raise ValueError('conv3d_valid_leaky_backward: dy %s and y %s differ in shape' % (tuple(dy.shape), tuple(y.shape)))
+    n, cout, so = y.shape[0], y.shape[1], y.shape[2]
+    lib = _lib.load()
+    dz = torch.empty_like(y)
+    db = torch.empty(cout, dtype=torch.float32, device=y.device)
+    ws = _workspace(y.device, lib.rf_conv3d_valid_leaky_backward_ws_bytes(n, cout, so))
+    _lib.check(lib.rf_conv3d_valid_leaky_backward(_p(dy), _p(y), n, cout, so, slope, _p(dz), _p(db), _p(ws), ws.numel(), _stream()),
+               'rf_conv3d_valid_leaky_backward')
+    return dz, db
+
+
+def pack_convv_dgrad_weight(w):
+    """OIDHW -> [k^3][cout -> 4][cin -> 16], zero padded: the A operand image of rf_conv3d_valid_dgrad (a permute and a pad)"""
+    _req(w.detach(), 'conv weight')
+    cout, cin, k = w.shape[0], w.shape[1], w.shape[2]
+    out = torch.zeros((k ** 3, (cout + 3) // 4 * 4, (cin + 15) // 16 * 16), dtype=torch.float32, device=w.device)
+    out[:, :cout, :cin] = w.detach().reshape(cout, cin, k ** 3).permute(2, 0, 1)
+    assert out.numel() == _lib.load().rf_convv_dgrad_packed_floats(cout, cin, k)
+    return out
+
+
+@_device_scoped
+def conv3d_valid_dgrad(dz, wd_packed, cin, k, stride, s):
+    """data gradient of the valid strided conv: dz [n, cout, so^3] -> dx [n, cin, s^3] (wd_packed from pack_convv_dgrad_weight); planes of x that no
+    output reads get 0"""
+    _req(dz, 'dz'), _req(wd_packed, 'wd_packed')
+    n, cout, so = dz.shape[0], dz.shape[1], dz.shape[2]
+    dx = torch.empty((n, cin, s, s, s), dtype=torch.float32, device=dz.device)
+    _lib.check(_lib.load().rf_conv3d_valid_dgrad(_p(dz), n, cout, so, _p(wd_packed), cin, k, stride, s, _p(dx), _stream()), 'rf_conv3d_valid_dgrad')
+    return dx
+
+
+@_device_scoped
+def conv3d_valid_wgrad(x, dz, k, stride):
+    """weight gradient of the valid strided conv: x [n, cin, s^3], dz [n, cout, so^3] -> dW [cout, cin, k, k, k] (split K, float64 slice sum)"""
+    _req(x, 'x'), _req(dz, 'dz')
+    n, cin, s = x.shape[0], x.shape[1], x.shape[2]
+    cout, so = dz.shape[1], dz.shape[2]
+    if dz.shape[0] != n or so != (s - k) // stride + 1:
+        raise ValueError('conv3d_valid_wgrad: dz %s does not match x %s, k %d, stride %d' % (tuple(dz.shape), tuple(x.shape), k, stride))
+    lib = _lib.load()
+    dw = torch.empty((cout, cin, k, k, k), dtype=torch.float32, device=x.device)
+    ws = _workspace(x.device, lib.rf_conv3d_valid_wgrad_ws_bytes(n, cin, cout, so, k))
+    _lib.check(lib.rf_conv3d_valid_wgrad(_p(x), n, cin, s, _p(dz), cout, k, stride, _p(dw), _p(ws), ws.numel(), _stream()), 'rf_conv3d_valid_wgrad')
+    return dw
 
 
 # --------------------------------------------------------------------------------------------------- fold / unfold
