@@ -18,6 +18,7 @@
 // ([kb][ib][lane][r] = W[16*ib + (lane&15)][16*kb + 4*(lane>>4) + r]) and the activations are consumed where they are.
 #include "common.h"
 #include "attn_row.h"
+#include "split_operand.h"
 
 // The scalar arithmetic here restates torch expressions op by op (every product and sum rounded).  This file is built
 // with -ffp-contract=off (csrc/build.py): hipcc's default -ffp-contract=fast fuses a*b+c in the backend, where neither
@@ -229,14 +230,10 @@ __global__ __launch_bounds__(AM_WAVES * 64) void k_attn_mlp(AmArgs a) {
 
 // ------------------------------------------------------------------------------------------------ fused MLP, split-operand form
 // The same encoder on the F16 matrix cores with every fp32 operand carried as two f16 pieces (x = h + l / 2^11, exact products, hi / lo
-// fp32 accumulators: csrc/conv3d_up_split.hip has the numerics).  A k-step of v_mfma_f32_16x16x32_f16 is 32 input features; lane group
+// fp32 accumulators: split_operand.h has the format and its numerics).  A k-step of v_mfma_f32_16x16x32_f16 is 32 input features; lane group
 // g supplies 8 of them and holds, after a layer, 4 features of every 16-feature output block -- so k-step t is made of the output
 // blocks 2t and 2t+1 (contraction order k <-> {16*(2t) + 4g + r, 16*(2t+1) + 4g + r}), the weight image is packed in that order, and
 // the activations again never leave registers: bias, LeakyReLU and the split run on the D registers in place.
-typedef _Float16 am_h8 __attribute__((ext_vector_type(8)));
-#define AMS_ACT 0.0625f
-#define AMS_W 16.0f
-#define AMS_LO 2048.0f
 
 // split image, in 16-byte fragments rows of 64 lanes: layer L at ams_layer_off(L): [t][ib][h|l][lane]
 static __host__ __device__ inline int ams_steps(int n_in, int layer) { return layer == 0 ? (n_in / 16 + 1) / 2 : 4; }
@@ -264,16 +261,15 @@ __global__ void k_attn_mlp_split_pack(AmsPackArgs a) {
         const int lane = (int)(li & 63), piece = (int)((li >> 6) & 1);
         const int ib = (int)((li >> 7) % ibn), t = (int)((li >> 7) / ibn);
         const int feat = ib * 16 + (lane & 15), g = lane >> 4;
-        am_h8 out;
+        h8 out;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const int k = 16 * (2 * t + (j >> 2)) + 4 * g + (j & 3);
-            double v = k < nin ? (double)a.w[layer][(size_t)feat * nin + k] * (double)AMS_W : 0.0;
-            v = v > 65504.0 ? 65504.0 : (v < -65504.0 ? -65504.0 : v);
-            const _Float16 h = (_Float16)(float)v;
-            out[j] = piece == 0 ? h : (_Float16)(float)((v - (double)(float)h) * (double)AMS_LO);
+            _Float16 h, l;
+            rf_split_weight(k < nin ? (double)a.w[layer][(size_t)feat * nin + k] : 0.0, h, l);
+            out[j] = piece == 0 ? h : l;
         }
-        reinterpret_cast<am_h8*>(a.img)[i] = out;
+        reinterpret_cast<h8*>(a.img)[i] = out;
     }
 }
 
@@ -288,30 +284,31 @@ extern "C" int rf_attn_mlp_split_pack(const float* w1, const float* w2, const fl
 }
 
 // 4 activation values (one D register quartet) -> 4 halves of the h and of the l piece, at positions o..o+3.  On register PAIRS (v_pk_mul_f32 for the two
-// scalings; round 6: 190 fewer VALU instructions per 16-row tile of ~2400, -2 % time).  Same operations, same roundings, same bits as the scalar form.
+// scalings; round 6: 190 fewer VALU instructions per 16-row tile of ~2400, -2 % time).  Same operations, same roundings, same bits as rf_split_at;
+// kept local because rf_split_at works on single values.
 typedef float am_f2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void ams_split4(const f32x4& v, am_h8& h, am_h8& l, int o) {
+__device__ __forceinline__ void ams_split4(const f32x4& v, h8& h, h8& l, int o) {
 #pragma unroll
     for (int e = 0; e < 4; e += 2) {
-        const am_f2 s2 = (am_f2){v[e], v[e + 1]} * (am_f2){AMS_ACT, AMS_ACT};
+        const am_f2 s2 = (am_f2){v[e], v[e + 1]} * (am_f2){SPLIT_ACT_SCALE, SPLIT_ACT_SCALE};
         am_f2 x;
         x.x = rf_clamp_f16(s2.x);
         x.y = rf_clamp_f16(s2.y);
-        const am_f2 xl = x * (am_f2){AMS_LO, AMS_LO};
+        const am_f2 xl = x * (am_f2){SPLIT_LO, SPLIT_LO};
         const _Float16 ha = (_Float16)x.x, hb = (_Float16)x.y;
         h[o + e] = ha; h[o + e + 1] = hb;
-        l[o + e] = (_Float16)fmaf(-AMS_LO, (float)ha, xl.x);        // (x - h) * 2^11: exact either way, one v_fma_mix instead of cvt + sub + mul
-        l[o + e + 1] = (_Float16)fmaf(-AMS_LO, (float)hb, xl.y);
+        l[o + e] = (_Float16)fmaf(-SPLIT_LO, (float)ha, xl.x);        // (x - h) * 2^11: exact either way, one v_fma_mix instead of cvt + sub + mul
+        l[o + e + 1] = (_Float16)fmaf(-SPLIT_LO, (float)hb, xl.y);
     }
 }
 
 // one layer, transposed: hi/lo[ib] = W[ib-block][k-step t] . (bh, bl)[t]; weight fragments from LDS, one (t, ib) pair ahead
 template <int IB>
-__device__ __forceinline__ void ams_layer(const float* wbuf, int tn, const am_h8 (&bh)[4], const am_h8 (&bl)[4], f32x4 (&hi)[8], f32x4 (&lo)[8], int lane) {
-    const am_h8* wv = reinterpret_cast<const am_h8*>(wbuf) + lane;
+__device__ __forceinline__ void ams_layer(const float* wbuf, int tn, const h8 (&bh)[4], const h8 (&bl)[4], f32x4 (&hi)[8], f32x4 (&lo)[8], int lane) {
+    const h8* wv = reinterpret_cast<const h8*>(wbuf) + lane;
 #pragma unroll
     for (int ib = 0; ib < IB; ++ib) { hi[ib] = (f32x4){0.f, 0.f, 0.f, 0.f}; lo[ib] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
-    am_h8 wh[2], wl[2];
+    h8 wh[2], wl[2];
     wh[0] = wv[0]; wl[0] = wv[64];
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
@@ -356,9 +353,9 @@ __global__ __launch_bounds__(AMS_WAVES * 64) void k_attn_mlp_split(AmArgs a) {
         if (row >= a.nrows) row = a.nrows - 1;                        // clamp: computed, never stored
         if (row < 0) row = 0;
         size_t orow = (size_t)row;
-        am_h8 bh[4], bl[4];
+        h8 bh[4], bl[4];
 #pragma unroll
-        for (int t = 0; t < 4; ++t) { bh[t] = (am_h8){0, 0, 0, 0, 0, 0, 0, 0}; bl[t] = bh[t]; }
+        for (int t = 0; t < 4; ++t) { bh[t] = (h8){0, 0, 0, 0, 0, 0, 0, 0}; bl[t] = bh[t]; }
         if (a.mode == 0) {
             const float* p = a.src + (size_t)row * a.n_in + 4 * g;
 #pragma unroll
@@ -402,7 +399,7 @@ __global__ __launch_bounds__(AMS_WAVES * 64) void k_attn_mlp_split(AmArgs a) {
                 for (int ib = 0; ib < 8; ++ib) {                       // bias + LeakyReLU(0.01) + split: the next layer's B operands
                     const float4 bz = bias4[layer * 32 + ib * 4 + g];
                     // (pairs: v_pk_fma_f32 / v_pk_add_f32 / v_pk_mul_f32; LeakyReLU as max(v, 0.01 v): the same value for every v, signed zeros and NaN included)
-                    const am_f2 c2 = {1.0f / AMS_LO, 1.0f / AMS_LO}, s2 = {0.01f, 0.01f};
+                    const am_f2 c2 = {1.0f / SPLIT_LO, 1.0f / SPLIT_LO}, s2 = {0.01f, 0.01f};
                     const am_f2 va = __builtin_elementwise_fma((am_f2){lo[ib][0], lo[ib][1]}, c2, (am_f2){hi[ib][0], hi[ib][1]}) + (am_f2){bz.x, bz.y};
                     const am_f2 vb = __builtin_elementwise_fma((am_f2){lo[ib][2], lo[ib][3]}, c2, (am_f2){hi[ib][2], hi[ib][3]}) + (am_f2){bz.z, bz.w};
                     const am_f2 na = va * s2, nb = vb * s2;
@@ -415,8 +412,8 @@ __global__ __launch_bounds__(AMS_WAVES * 64) void k_attn_mlp_split(AmArgs a) {
 #pragma unroll
                     for (int ib = 0; ib < 2; ++ib) {
                         const float4 bz = bias4[3 * 32 + ib * 4 + g];
-                        const float4 o = make_float4(fmaf(lo[ib][0], 1.0f / AMS_LO, hi[ib][0]) + bz.x, fmaf(lo[ib][1], 1.0f / AMS_LO, hi[ib][1]) + bz.y,
-                                                     fmaf(lo[ib][2], 1.0f / AMS_LO, hi[ib][2]) + bz.z, fmaf(lo[ib][3], 1.0f / AMS_LO, hi[ib][3]) + bz.w);
+                        const float4 o = make_float4(rf_split_join(hi[ib][0], lo[ib][0]) + bz.x, rf_split_join(hi[ib][1], lo[ib][1]) + bz.y,
+                                                     rf_split_join(hi[ib][2], lo[ib][2]) + bz.z, rf_split_join(hi[ib][3], lo[ib][3]) + bz.w);
                         *reinterpret_cast<float4*>(a.out + orow * AM_OUT + ib * 16 + 4 * g) = o;
                     }
                 }

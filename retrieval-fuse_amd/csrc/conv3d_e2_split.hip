@@ -17,14 +17,12 @@
 // GroupNorm statistics of the output (sum, sum of squares per (sample, cout): the 8 voxels of a cout are 8 neighbouring lanes) in float64.
 // The fp32 position-major kernels this replaces (k_conv3_mfma<2,2,2,16>, k_conv3_small<2,2>) took 125 / 94 us per launch on 8192 samples.
 #include "common.h"
-
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+#include "split_operand.h"
 
 namespace {
 constexpr int E2_NC = 256;                                   // columns per workgroup (32 couts)
 constexpr int E2_STEP_H8 = (E2_NC / 16) * 2 * 64;            // h8 elements of one k-step of one n-chunk: 2048 = 32 KB
 constexpr int E2_LDS_BYTES = 2 * E2_STEP_H8 * 16;            // 65,536
-constexpr float E2_ACT_SCALE = 1.0f / 16, E2_W_SCALE = 16.0f, E2_LO = 2048.0f;
 }
 
 // edge = 2: K = 8 cin, N = 8 cout (k-step = 4 channels x 8 voxels).  edge = 1: only the centre tap touches data: K = cin, N = cout (k-step = 32 channels).
@@ -58,10 +56,9 @@ __global__ void k_conv3_e2_split_pack(const float* __restrict__ w, int cout, int
                 const int co = col, ci = 32 * s + 8 * (lane >> 4) + u;
                 if (co < cout && ci < cin) val = (double)w[((size_t)co * cin + ci) * 27 + 13];
             }
-            val *= (double)E2_W_SCALE;
-            val = val > 65504.0 ? 65504.0 : (val < -65504.0 ? -65504.0 : val);
-            const _Float16 h = (_Float16)(float)val;
-            out[u] = piece == 0 ? h : (_Float16)(float)((val - (double)(float)h) * (double)E2_LO);
+            _Float16 h, l;
+            rf_split_weight(val, h, l);
+            out[u] = piece == 0 ? h : l;
         }
         wp[i] = out;
     }
@@ -120,11 +117,7 @@ __global__ __launch_bounds__(256, 2) void k_conv3_e2_split(E2Args a) {
     float4 xa[2][2], af[2];                                       // edge 2: the raw row and its affine, converted after the MFMAs they were loaded under
     h8 nah[2], nal[2];                                             // edge 1: converted at once (8 affines per row would not fit beside the accumulators)
     h8 wreg[8];
-    auto split1 = [](float y, _Float16& hh, _Float16& ll) {
-        const float v = rf_clamp_f16(y * E2_ACT_SCALE);
-        hh = (_Float16)v;
-        ll = (_Float16)fmaf(-E2_LO, (float)hh, v * E2_LO);
-    };
+    auto split1 = [](float y, _Float16& hh, _Float16& ll) { rf_split(y * SPLIT_ACT_SCALE, hh, ll); };     // a lambda: a direct call reorders the code
     auto load_step = [&](int s) {                                  // A rows and the B block of k-step s
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
@@ -204,7 +197,7 @@ __global__ __launch_bounds__(256, 2) void k_conv3_e2_split(E2Args a) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int sm = n0 + (2 * wm + i) * 16 + kg * 4 + r;
-                const float y = rf_relu(fmaf(lo[i][j][r], 1.0f / E2_LO, hi[i][j][r]));
+                const float y = rf_relu(rf_split_join(hi[i][j][r], lo[i][j][r]));
                 const bool live = sm < a.n && col < ncols;
                 if (live) a.out[(size_t)sm * ncols + col] = y;
                 if (a.stats) {                                      // the 8 voxels of a cout: lanes li & 7 = 0 .. 7 of the same row (wave-uniform branch)

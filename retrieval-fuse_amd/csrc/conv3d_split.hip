@@ -3,7 +3,7 @@
 // rf_conv3d_k3_gn_relu[_stats|_pool] (conv3d_mfma.hip), evaluated on the F16 matrix cores by OPERAND SPLITTING:
 //     x = h + l / 2^11,  h = f16(x),  l = f16((x - h) * 2^11);   a*b ~ ah*bh + (ah*bl + al*bh) / 2^11,   exact f16 x f16 products,
 //     fp32 accumulation in two separate accumulators (hi, lo), combined once in the epilogue
-// (see conv3d_up_split.hip for the numerics: half the rounding error of the fp32 MFMA chain at 5.3x its multiply-add rate).
+// (see split_operand.h for the numerics: half the rounding error of the fp32 MFMA chain at 5.3x its multiply-add rate).
 //
 // GEMM view: M = the 512 voxels of a box (8 waves x 4 m-blocks, voxel order = BoxOrder of conv_box.h so that the epilogue -- shared with
 // the fp32 kernel -- finds whole float4 rows and pooling cells in a lane), N = cout (NB = 1 or 2 n-blocks), K = cin * 27 walked in
@@ -46,10 +46,9 @@ __global__ void k_conv3_split_pack(const float* __restrict__ w, int cout, int ci
         for (int j = 0; j < 8; ++j) {
             double v = 0.0;
             if (i < nreal && tap < 27 && co < cout && ca * 8 + j < cin) v = (double)w[((size_t)co * cin + ca * 8 + j) * 27 + tap];   // channels past cin: zero
-            v *= (double)CS_W_SCALE;
-            v = v > 65504.0 ? 65504.0 : (v < -65504.0 ? -65504.0 : v);
-            const _Float16 h = (_Float16)(float)v;
-            out[j] = piece == 0 ? h : (_Float16)(float)((v - (double)(float)h) * (double)CS_LO);
+            _Float16 h, l;
+            rf_split_weight(v, h, l);
+            out[j] = piece == 0 ? h : l;
         }
         wp[i] = out;
     }
@@ -141,7 +140,7 @@ __global__ __launch_bounds__(512, WPS) void k_conv3_split(ConvArgs a, SplitPreOu
                     const float4 af = triple(ca * 8 + j);
                     y[j] = vin[r] ? fmaf(st.x[r][j] - af.x, af.y, af.z) : 0.f;
                 }
-                cs_split8(y, h, l);
+                rf_split8(y, h, l);
             }
             if (r == 0 || tid < CS_VOX - 512) {
                 unsigned char* p = lds + buf * CS_BUF + vslot[r];
@@ -223,7 +222,7 @@ __global__ __launch_bounds__(512, WPS) void k_conv3_split(ConvArgs a, SplitPreOu
             }
             __builtin_amdgcn_sched_barrier(0);
             hook(m);                                                   // VALU work of the next chunk's staging, issued in the shadow of this block's MFMAs
-            cs_mfma_block<NB>(hi[m], lo[m], ah[m & 1], al[m & 1], bh, bl);
+            rf_split_mfma<NB>(hi[m], lo[m], ah[m & 1], al[m & 1], bh, bl);
             __builtin_amdgcn_sched_barrier(0);
         }
     };
@@ -258,10 +257,7 @@ __global__ __launch_bounds__(512, WPS) void k_conv3_split(ConvArgs a, SplitPreOu
                 if constexpr (!ONE && !PRE) {
                     const int e = (s - 2) * 4 + m, r = e >> 3, j = e & 7;
                     const float y = vin[r] ? fmaf(x.x[r][j] - afn[j].x, afn[j].y, afn[j].z) : 0.f;
-                    const float v = rf_clamp_f16(y * CS_ACT_SCALE);
-                    const _Float16 hh = (_Float16)v;
-                    hq[r][j] = hh;
-                    lq[r][j] = (_Float16)fmaf(-CS_LO, (float)hh, v * CS_LO);
+                    rf_split_at(y * SPLIT_ACT_SCALE, hq[r], lq[r], j);
                 }
             };
             if (s == 0) kstep(std::true_type{}, xload, no_hook, ap, buf + tnext, ch, cl, nh, nl);
@@ -305,7 +301,7 @@ __global__ __launch_bounds__(512, WPS) void k_conv3_split(ConvArgs a, SplitPreOu
                     for (int r = 0; r < 4; ++r) {
                         int sdummy, z, y, x;
                         BoxOrder<8, 8, 8, 8, 4>::voxel(wave, m, 4 * (lane >> 4) + r, sdummy, z, y, x);
-                        e[col * CS_PO_STRIDE + (z * 8 + y) * 8 + x] = rf_max(fmaf(lo[m][0][r], 1.0f / CS_LO, hi[m][0][r]), a.floor);
+                        e[col * CS_PO_STRIDE + (z * 8 + y) * 8 + x] = rf_max(rf_split_join(hi[m][0][r], lo[m][0][r]), a.floor);
                     }
             }
             __syncthreads();
@@ -346,7 +342,7 @@ __global__ __launch_bounds__(512, WPS) void k_conv3_split(ConvArgs a, SplitPreOu
                     y[j] = fmaf(e[(sg * 8 + j) * CS_PO_STRIDE + tid] - t4.x, t4.y, t4.z);
                 }
                 h8 h, l;
-                cs_split8(y, h, l);
+                rf_split8(y, h, l);
                 o[(size_t)sg * 2 * 512] = h;
                 o[(size_t)sg * 2 * 512 + 512] = l;
             }
@@ -364,7 +360,7 @@ __global__ __launch_bounds__(512, WPS) void k_conv3_split(ConvArgs a, SplitPreOu
                     for (int r = 0; r < 4; ++r) {
                         int sdummy, z, y, x;
                         BoxOrder<8, 8, 8, 8, 4>::voxel(wave, m, 4 * (lane >> 4) + r, sdummy, z, y, x);
-                        e[col * CS_PO_STRIDE + (z * 8 + y) * 8 + x] = rf_max(fmaf(lo[m][0][r], 1.0f / CS_LO, hi[m][0][r]), a.floor);
+                        e[col * CS_PO_STRIDE + (z * 8 + y) * 8 + x] = rf_max(rf_split_join(hi[m][0][r], lo[m][0][r]), a.floor);
                     }
             }
             __syncthreads();
@@ -382,7 +378,7 @@ __global__ __launch_bounds__(512, WPS) void k_conv3_split(ConvArgs a, SplitPreOu
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) acc[m][nb][r] = fmaf(lo[m][nb][r], 1.0f / CS_LO, hi[m][nb][r]);
+            for (int r = 0; r < 4; ++r) acc[m][nb][r] = rf_split_join(hi[m][nb][r], lo[m][nb][r]);
     conv_box_epilogue<8, 8, 8, 1, 8, 4, NB, (size_t)CS_LDS_BYTES>(a, acc, reinterpret_cast<float*>(lds), tid, lane, wave, n0, z0, y0, x0, cob, lblock);
 }
 
@@ -431,7 +427,7 @@ __global__ __launch_bounds__(512, NB == 1 ? 4 : 2) void k_conv3_split_s4(ConvArg
             y[j] = fmaf(x[j] - af.x, af.y, af.z);
         }
         h8 h, l;
-        cs_split8(y, h, l);
+        rf_split8(y, h, l);
         *reinterpret_cast<h8*>(myslot) = h;
         *reinterpret_cast<h8*>(myslot + S4_PLANE) = l;
     };
@@ -479,7 +475,7 @@ __global__ __launch_bounds__(512, NB == 1 ? 4 : 2) void k_conv3_split_s4(ConvArg
                 if ((m == 0 && s < 2) || (m == 3 && s >= 5)) continue;      // every tap of the k-step reads the plane below / above the volume: zeros
                 const h8 ah = *reinterpret_cast<const h8*>(abase + m * 96 + atap[s]);
                 const h8 al = *reinterpret_cast<const h8*>(abase + m * 96 + atap[s] + S4_PLANE);
-                cs_mfma_block<NB>(hi[m], lo[m], ah, al, bh, bl);
+                rf_split_mfma<NB>(hi[m], lo[m], ah, al, bh, bl);
             }
 #pragma unroll
             for (int nb = 0; nb < NB; ++nb) { bh[nb] = nh[nb]; bl[nb] = nl[nb]; }
@@ -497,7 +493,7 @@ __global__ __launch_bounds__(512, NB == 1 ? 4 : 2) void k_conv3_split_s4(ConvArg
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) acc[m][nb][r] = fmaf(lo[m][nb][r], 1.0f / CS_LO, hi[m][nb][r]);
+            for (int r = 0; r < 4; ++r) acc[m][nb][r] = rf_split_join(hi[m][nb][r], lo[m][nb][r]);
     conv_box_epilogue<4, 4, 4, 8, 8, 4, NB, (size_t)S4_LDS_BYTES>(a, acc, reinterpret_cast<float*>(lds), tid, lane, wave, n0, 0, 0, 0, cob, lblock);
 }
 
@@ -643,10 +639,10 @@ __global__ __launch_bounds__(512, 4) void k_conv3_cin1_presplit(Cin1PreArgs a) {
     for (int cp = 0; cp < 4; ++cp) {
         const float4 t0 = nxt[2 * cp], t1 = nxt[2 * cp + 1];
         negc[cp] = (f32x2){-t0.x, -t1.x};
-        sc[cp] = (f32x2){t0.y * CS_ACT_SCALE, t1.y * CS_ACT_SCALE};
-        sh[cp] = (f32x2){t0.z * CS_ACT_SCALE, t1.z * CS_ACT_SCALE};
+        sc[cp] = (f32x2){t0.y * SPLIT_ACT_SCALE, t1.y * SPLIT_ACT_SCALE};
+        sh[cp] = (f32x2){t0.z * SPLIT_ACT_SCALE, t1.z * SPLIT_ACT_SCALE};
     }
-    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+    typedef _Float16 h2 __attribute__((ext_vector_type(2)));          // local split form: pairs by subtraction, v_cvt_pk_f16_f32 both ways (above)
     unsigned char* outp = a.out + (size_t)nn * 2 * VOL * 16;
 #pragma unroll
     for (int z = 0; z < 8; ++z) {
@@ -659,7 +655,7 @@ __global__ __launch_bounds__(512, 4) void k_conv3_cin1_presplit(Cin1PreArgs a) {
             v[1] = rf_clamp_f16(v[1]);
             const h2 hh = __builtin_convertvector(v, h2);
             const f32x2 back = __builtin_convertvector(hh, f32x2);
-            const h2 ll = __builtin_convertvector((v - back) * CS_LO, h2);      // v - h is exact in fp32
+            const h2 ll = __builtin_convertvector((v - back) * SPLIT_LO, h2);      // v - h is exact in fp32
             h[2 * cp] = hh[0]; h[2 * cp + 1] = hh[1];
             l[2 * cp] = ll[0]; l[2 * cp + 1] = ll[1];
         }
@@ -705,9 +701,6 @@ extern "C" int rf_conv3d_split_supported(int c0, int c1, int n, int edge, int co
     if (cout16 <= 32) return rf_conv_use_big(n, edge, cout16) || boxes >= 256;
     // more couts (round 6; the deep levels of the chunk-level U-Nets: 24 -> 48 @32^3, 48 -> 96 and 96 -> 96 @16^3 at 16 chunks): cout blocks of 16 / 32 on grid.y, every block
     // staging the box again -- still a third of the fp32-MFMA form's time (C5: 0.33 / 0.18 / 0.34 ms) as long as the launch has a couple of workgroups per CU
-#ifdef RF_SPLIT_NARROW_ONLY                                          // dev A/B (tools/build_variant.py): rounds 2-5's rule
-    return 0;
-#endif
     return cout16 <= 192 && boxes * (cout16 / 16) >= 512;
 }
 
@@ -737,9 +730,9 @@ static int split_run(const ConvArgs& a, void* stream) {
         RF_REQUIRE(!a.pool_out, RF_E_UNSUPPORTED, "rf_conv3d_split_k3_gn_relu: the 4^3 form has no fused max-pool (pool its output with rf_maxpool3d_2_stats)");
         // all couts of a 32 / 64-cout layer in one workgroup (samples staged once; 4^3 levels of the retrieval backbone: 32 -> 32, 32 -> 64, 64 -> 64)
         const unsigned gx = (unsigned)((n + 7) / 8), nbt = (unsigned)(a.cout16 / 16);
-        if (CS_S4_WIDE && nbt % 4 == 0) hipLaunchKernelGGL(k_conv3_split_s4<4>, dim3(gx, nbt / 4), dim3(512), S4_LDS_BYTES, (hipStream_t)stream, a);
-        else if (CS_S4_WIDE && nbt % 3 == 0) hipLaunchKernelGGL(k_conv3_split_s4<3>, dim3(gx, nbt / 3), dim3(512), S4_LDS_BYTES, (hipStream_t)stream, a);      // nf = 12: 48 / 96 couts
-        else if (CS_S4_WIDE && nbt % 2 == 0) hipLaunchKernelGGL(k_conv3_split_s4<2>, dim3(gx, nbt / 2), dim3(512), S4_LDS_BYTES, (hipStream_t)stream, a);
+        if (nbt % 4 == 0) hipLaunchKernelGGL(k_conv3_split_s4<4>, dim3(gx, nbt / 4), dim3(512), S4_LDS_BYTES, (hipStream_t)stream, a);
+        else if (nbt % 3 == 0) hipLaunchKernelGGL(k_conv3_split_s4<3>, dim3(gx, nbt / 3), dim3(512), S4_LDS_BYTES, (hipStream_t)stream, a);      // nf = 12: 48 / 96 couts
+        else if (nbt % 2 == 0) hipLaunchKernelGGL(k_conv3_split_s4<2>, dim3(gx, nbt / 2), dim3(512), S4_LDS_BYTES, (hipStream_t)stream, a);
         else hipLaunchKernelGGL(k_conv3_split_s4<1>, dim3(gx, nbt), dim3(512), S4_LDS_BYTES, (hipStream_t)stream, a);
         RF_CHECK_LAUNCH("rf_conv3d_split_k3_gn_relu");
         return RF_OK;

@@ -170,7 +170,7 @@ __global__ __launch_bounds__(512, 4) void k_conv3_split_zc(ConvArgs a, SplitPreO
 #pragma unroll
         for (int m = 0; m < 4; ++m)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) acc[m][r] = fmaf(lo[m][r], 1.0f / CS_LO, hi[m][r]);
+            for (int r = 0; r < 4; ++r) acc[m][r] = rf_split_join(hi[m][r], lo[m][r]);
     };
 
     // ---- outputs of one box from the accumulators.  D tile: col = lane & 15 = cout, rows 4 (lane >> 4) + r = voxel i: x = i & 7, y = 2 yq + (i >> 3)
@@ -316,7 +316,7 @@ __global__ __launch_bounds__(512, 4) void k_conv3_split_zc(ConvArgs a, SplitPreO
                     y[j] = fmaf(__hip_atomic_load(pv + (sg * 8 + j) * PVOL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - t4.x, t4.y, t4.z);
                 }
                 h8 h, l;
-                cs_split8(y, h, l);
+                rf_split8(y, h, l);
                 o[(size_t)sg * 2 * PVOL] = h;
                 o[(size_t)sg * 2 * PVOL + PVOL] = l;
             }
@@ -430,7 +430,7 @@ __global__ __launch_bounds__(512, 4) void k_conv3_split_zcm(ConvArgs a, SplitPre
                 float y[8];
 #pragma unroll
                 for (int j = 0; j < 8; ++j) y[j] = st.in[r] ? fmaf(st.x[r][j] - af[j].x, af[j].y, af[j].z) : 0.f;
-                cs_split8(y, h, l);
+                rf_split8(y, h, l);
             }
             if (r == 0 || tid < CS_VOX - 512) {
                 *reinterpret_cast<h8*>(img + vslot[r]) = h;
@@ -545,7 +545,7 @@ __global__ __launch_bounds__(512, 4) void k_conv3_split_zcm(ConvArgs a, SplitPre
 #pragma unroll
                 for (int m = 0; m < 4; ++m)
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) hi[m][r] = rf_max(fmaf(lo[m][r], 1.0f / CS_LO, hi[m][r]), a.floor);      // the box's output values
+                    for (int r = 0; r < 4; ++r) hi[m][r] = rf_max(rf_split_join(hi[m][r], lo[m][r]), a.floor);      // the box's output values
             }
             if (EPI == 0 && last) {
                 // outputs straight from the accumulators: D tile col = lane & 15 = cout, rows 4 (lane >> 4) + r = voxel x = i & 7, y = 2 yq + (i >> 3).
@@ -683,7 +683,7 @@ __global__ __launch_bounds__(512, 4) void k_conv3_split_zcm(ConvArgs a, SplitPre
                             y[j] = fmaf(e[(sg * 8 + j) * ZM_TILE_STRIDE + tv] - t4.x, t4.y, t4.z);
                         }
                         h8 h, l;
-                        cs_split8(y, h, l);
+                        rf_split8(y, h, l);
                         o[(size_t)sg * 2 * 512] = h;
                         o[(size_t)sg * 2 * 512 + 512] = l;
                     }

@@ -1,19 +1,8 @@
 // rf_conv3d_up_split_k3_gn_relu: the decoder form of SingleConv 'gcr' (reference model/unet.py:19-76 with the nearest x2 upsample +
 // concat of :297-308 / :354-360) on whole 8^3 samples -- the same arithmetic contract as rf_conv3d_up_k3_gn_relu (conv3d_up.hip:
 // upsampled channels convolved in LOW resolution with 8 pre-summed taps per output parity), evaluated on the F16 matrix cores by
-// OPERAND SPLITTING instead of on v_mfma_f32_16x16x4_f32:
-//
-//     every fp32 operand x is carried as two f16 numbers   h = f16(x),  l = f16((x - h) * 2^11)       (x - h is exact in fp32)
-//     so that x = h + l / 2^11 up to 2^-22 |x|, and        a * b  ~  ah * bh  +  (ah * bl + al * bh) / 2^11  (al * bl: 2^-22 relative, dropped).
-//     An f16 x f16 product is exact in fp32.  v_mfma_f32_16x16x32_f16 accumulates in fp32; the ah*bh sums and the cross sums go to
-//     SEPARATE accumulators (hi, lo) and meet once, in the epilogue:  out = hi + lo / 2^11.
-//
-// Three f16 MFMAs (16 cycles each for 16x16x32) replace eight fp32 MFMAs (32 cycles each for 16x16x4): 5.3x the multiply-add rate of the
-// fp32 matrix path at -- measured, tools/micro/split_probe.hip -- HALF its rounding error against float64 (K = 216 ... 5184: rms 1.2e-8
-// vs 2.5e-8 of sum|a b|, max 9.7e-8 vs 3.1e-7): the fp32 MFMA is a sequential fmaf chain with one rounding per product, the f16 MFMA
-// rounds once per 32 products, and the 2^-22 representation error of the operands is random per element and does not accumulate.
-// Activations are scaled by 2^-4 and weights by 2^4 before the split (exact): f16 overflows at 65504, so a GroupNorm output would have to
-// exceed 1e6 to saturate (it is clamped, never inf), while small values lose nothing (whatever h drops, l carries).
+// OPERAND SPLITTING instead of on v_mfma_f32_16x16x4_f32
+// (split_operand.h: the format, its scales and its error against float64).
 //
 // Work split (as conv3d_up.hip): one workgroup of 8 waves per sample, WAVE w OWNS OUTPUT PARITY w = (pz,py,px): its 4 m-blocks are the
 // four z planes of that parity's 4^3 lattice (m-block row r = (Y,X) = (r >> 2, r & 3)), all couts (NB n-blocks of 16) -> 16 output tiles,
@@ -35,9 +24,8 @@
 // statistics of the output (float64, fixed order) for the next layer -- or (rf_conv3d_up_split_presplit) the next layer's GroupNorm applied on
 // the spot and the output written pre-split.
 #include "common.h"
+#include "split_operand.h"
 #include <type_traits>
-
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 
 namespace {
 constexpr int US_SY = 12, US_SZ = 120, US_ASLOTS = 1208;        // full-res halo box, slot(z,y,x) = z*120 + y*12 + x (x, y, z in 0..9)
@@ -51,8 +39,7 @@ constexpr int US_LDS_BYTES = US_B_OFF + US_MAX_CGB * 2 * US_B_PLANE;      // 132
 constexpr int US_PRE_STATS = US_LDS_BYTES, US_PRE_TRIPLES = US_PRE_STATS + 64 * 16;     // pre-split epilogue: per-channel (sum, sum of squares), then triples
 constexpr int US_LDS_ALLOC = US_PRE_TRIPLES + 64 * 16;                                     // 134,656
 constexpr int US_T_STRIDE = 517;                                 // epilogue tile row (floats) of the whole-sample kernel: odd (bank-conflict-free scalar writes)
-constexpr float US_ACT_SCALE = 1.0f / 16, US_W_SCALE = 16.0f, US_LO = 2048.0f;
-constexpr bool US_ZSKIP = true, US_S4_WIDE = true;
+constexpr bool US_ZSKIP = true;
 static_assert(64 * US_T_STRIDE * 4 <= US_LDS_BYTES, "epilogue tile must fit");
 }   // namespace
 
@@ -98,10 +85,9 @@ __global__ void k_conv3_up_split_pack(const float* __restrict__ w, int cout, int
                             for (int dx = x_lo; dx <= x_hi; ++dx) v += (double)wk[(dz * 3 + dy) * 3 + dx];      // float64 sum, split from it
                 }
             }
-            v *= (double)US_W_SCALE;
-            v = v > 65504.0 ? 65504.0 : (v < -65504.0 ? -65504.0 : v);
-            const _Float16 h = (_Float16)(float)v;
-            out[j] = piece == 0 ? h : (_Float16)(float)((v - (double)(float)h) * (double)US_LO);
+            _Float16 h, l;
+            rf_split_weight(v, h, l);
+            out[j] = piece == 0 ? h : l;
         }
         wp[i] = out;
     }
@@ -142,39 +128,6 @@ struct UpSplitArgs {
     int pre_pm;
 };
 
-// 8 normalised channel values of one voxel -> the two f16 pieces (scaled by 2^-4; saturating, never inf)
-__device__ __forceinline__ void us_split8(const float (&y)[8], h8& h, h8& l) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const float v = rf_clamp_f16(y[j] * US_ACT_SCALE);
-        const _Float16 hh = (_Float16)v;
-        h[j] = hh;
-        l[j] = (_Float16)fmaf(-US_LO, (float)hh, v * US_LO);          // (v - h) * 2^11: exact either way, one v_fma_mix instead of cvt + sub + mul
-    }
-}
-
-// ... of values that already carry the 2^-4 (folded into the GroupNorm triple: (x - c) (s / 16) + b / 16 rounds like ((x - c) s + b) / 16)
-__device__ __forceinline__ void us_split8_scaled(const float (&y)[8], h8& h, h8& l) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const float v = rf_clamp_f16(y[j]);
-        const _Float16 hh = (_Float16)v;
-        h[j] = hh;
-        l[j] = (_Float16)fmaf(-US_LO, (float)hh, v * US_LO);
-    }
-}
-
-template <int NB>
-__device__ __forceinline__ void us_mfma_block(f32x4 (&hi)[NB], f32x4 (&lo)[NB], const h8& ah, const h8& al, const h8 (&bh)[NB], const h8 (&bl)[NB]) {
-    // three passes over the n-blocks: consecutive MFMAs never share an accumulator
-#pragma unroll
-    for (int n = 0; n < NB; ++n) hi[n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh[n], hi[n], 0, 0, 0);
-#pragma unroll
-    for (int n = 0; n < NB; ++n) lo[n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl[n], lo[n], 0, 0, 0);
-#pragma unroll
-    for (int n = 0; n < NB; ++n) lo[n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh[n], lo[n], 0, 0, 0);
-}
-
 template <int NB>
 __global__ __launch_bounds__(512, 2) void k_conv3_up_split(UpSplitArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
@@ -213,7 +166,7 @@ __global__ __launch_bounds__(512, 2) void k_conv3_up_split(UpSplitArgs a) {
             y[j] = fmaf((cg == wave ? xl[j] : a.src1[((size_t)n * c1 + cg * 8 + j) * 64 + lane]) - af.x, af.y, af.z);
         }
         h8 h, l;
-        us_split8(y, h, l);
+        rf_split8(y, h, l);
         const int slot = ((lane >> 4) + 1) * US_BZ + (((lane >> 2) & 3) + 1) * US_BY + (lane & 3) + 1;
         unsigned char* p = lds + US_B_OFF + cg * 2 * US_B_PLANE + slot * 16;
         *reinterpret_cast<h8*>(p) = h;
@@ -229,7 +182,7 @@ __global__ __launch_bounds__(512, 2) void k_conv3_up_split(UpSplitArgs a) {
             y[j] = fmaf(x[j] - af.x, af.y, af.z);
         }
         h8 h, l;
-        us_split8(y, h, l);
+        rf_split8(y, h, l);
         unsigned char* p = lds + (ca & 1) * US_A_BUF + vslot * 16;
         *reinterpret_cast<h8*>(p) = h;
         *reinterpret_cast<h8*>(p + US_A_PLANE) = l;
@@ -294,7 +247,7 @@ __global__ __launch_bounds__(512, 2) void k_conv3_up_split(UpSplitArgs a) {
                 al[0] = *reinterpret_cast<const h8*>(pre + lplane);
             }
             __builtin_amdgcn_sched_barrier(0);
-            if (m != decltype(skip_m)::value) us_mfma_block<NB>(hi[m], lo[m], ah[m & 1], al[m & 1], bh, bl);
+            if (m != decltype(skip_m)::value) rf_split_mfma<NB>(hi[m], lo[m], ah[m & 1], al[m & 1], bh, bl);
             __builtin_amdgcn_sched_barrier(0);
         }
     };
@@ -338,7 +291,7 @@ __global__ __launch_bounds__(512, 2) void k_conv3_up_split(UpSplitArgs a) {
                     y[j] = fmaf(x[j] - af.x, af.y, af.z);
                 }
                 h8 h, l;
-                us_split8(y, h, l);
+                rf_split8(y, h, l);
                 unsigned char* p = lds + ((ca + 1) & 1) * US_A_BUF + (vslot + half * 4 * US_SZ) * 16;
                 *reinterpret_cast<h8*>(p) = h;
                 *reinterpret_cast<h8*>(p + US_A_PLANE) = l;
@@ -398,7 +351,7 @@ __global__ __launch_bounds__(512, 2) void k_conv3_up_split(UpSplitArgs a) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int lin = (2 * m + pz) * 64 + (2 * yj + py) * 8 + 2 * r + px;
-                    e[(nb * 16 + col) * US_T_STRIDE + lin] = rf_relu(fmaf(lo[m][nb][r], 1.0f / US_LO, hi[m][nb][r]));
+                    e[(nb * 16 + col) * US_T_STRIDE + lin] = rf_relu(rf_split_join(hi[m][nb][r], lo[m][nb][r]));
                 }
     }
     __syncthreads();
@@ -444,7 +397,7 @@ __global__ __launch_bounds__(512, 2) void k_conv3_up_split(UpSplitArgs a) {
                 y[j] = fmaf(e[(sg * 8 + j) * US_T_STRIDE + te] - t4.x, t4.y, t4.z);
             }
             h8 h, l;
-            us_split8(y, h, l);
+            rf_split8(y, h, l);
             po[(size_t)sg * 2 * 512] = h;
             po[(size_t)sg * 2 * 512 + 512] = l;
         }
@@ -582,7 +535,7 @@ __global__ __launch_bounds__(512, 2) void k_conv3_up_split_pp(UpSplitArgs a) {
                 y[j] = fmaf(xl[j] - af.x, af.y, af.z);
             }
             h8 h, l;
-            us_split8(y, h, l);
+            rf_split8(y, h, l);
             const int slot = ((lane >> 4) + 1) * US_BZ + (((lane >> 2) & 3) + 1) * US_BY + (lane & 3) + 1;
             unsigned char* p = lds + US_B_OFF + cg * 2 * US_B_PLANE + slot * 16;
             *reinterpret_cast<h8*>(p) = h;
@@ -596,7 +549,7 @@ __global__ __launch_bounds__(512, 2) void k_conv3_up_split_pp(UpSplitArgs a) {
                 y[j] = fmaf(x0[j] - af.x, af.y, af.z);
             }
             h8 h, l;
-            us_split8(y, h, l);
+            rf_split8(y, h, l);
             const int vs = ((tid >> 6) + 1) * US_SZ + (((tid >> 3) & 7) + 1) * US_SY + (tid & 7) + 1;
             unsigned char* p = lds + vs * 16;
             *reinterpret_cast<h8*>(p) = h;
@@ -797,7 +750,7 @@ __global__ __launch_bounds__(512, 2) void k_conv3_up_split_pp(UpSplitArgs a) {
                     __builtin_amdgcn_sched_barrier(0);
                     normalise8(x, more ? sp : sp ^ 1, cx * 8);
                     h8 h, l;
-                    us_split8(x, h, l);
+                    rf_split8(x, h, l);
                     int vs = tid;
                     asm volatile("" : "+v"(vs));
                     const int tix = vs;
@@ -817,7 +770,7 @@ __global__ __launch_bounds__(512, 2) void k_conv3_up_split_pp(UpSplitArgs a) {
                     __builtin_amdgcn_sched_barrier(0);
                     normalise8(x, sp ^ 1, c0 + cgb * 8);
                     h8 h, l;
-                    us_split8(x, h, l);
+                    rf_split8(x, h, l);
                     int ls = tid;
                     asm volatile("" : "+v"(ls));
                     ls = (((ls >> 4) & 3) + 1) * US_BZ + (((ls >> 2) & 3) + 1) * US_BY + (ls & 3) + 1;
@@ -878,7 +831,7 @@ __global__ __launch_bounds__(512, 2) void k_conv3_up_split_pp(UpSplitArgs a) {
 #pragma unroll
             for (int j = 0; j < 2; ++j)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) hi[vb][j][r] = rf_relu(fmaf(lo[vb][j][r], 1.0f / US_LO, hi[vb][j][r]));
+                for (int r = 0; r < 4; ++r) hi[vb][j][r] = rf_relu(rf_split_join(hi[vb][j][r], lo[vb][j][r]));
         double2* chst = reinterpret_cast<double2*>(lds + PP_CHST);
         double2* chs = reinterpret_cast<double2*>(lds + PP_CHS);
         float4* trip = reinterpret_cast<float4*>(lds + PP_TRIP);
@@ -932,7 +885,7 @@ __global__ __launch_bounds__(512, 2) void k_conv3_up_split_pp(UpSplitArgs a) {
             rs = rs * (1.5 - 0.5 * xv * rs * rs);
             const float2 gb = reinterpret_cast<const float2*>(lds + PP_GB)[te];
             float4 t4 = gn_affine(mean, rs, gb.x, gb.y);
-            t4.y *= US_ACT_SCALE; t4.z *= US_ACT_SCALE;              // the split's 2^-4, exact
+            t4.y *= SPLIT_ACT_SCALE; t4.z *= SPLIT_ACT_SCALE;              // the split's 2^-4, exact
             trip[te] = t4;
         }
         PP_STAMP(8);
@@ -953,7 +906,8 @@ __global__ __launch_bounds__(512, 2) void k_conv3_up_split_pp(UpSplitArgs a) {
 #pragma unroll
                 for (int i = 0; i < 8; ++i) y[i] = fmaf(hi[vb][i >> 2][i & 3] - t4[i].x, t4[i].y, t4[i].z);
                 h8 h, l;
-                us_split8_scaled(y, h, l);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) rf_split_at(y[j], h, l, j);     // the 2^-4 is in the triple: (x - c) (s / 16) + b / 16 rounds like ((x - c) s + b) / 16
                 const int so = a.pre_pm ? (vb & 1) * 256 + (vb >> 1) * 16 : vb * 64;
                 if (sg < nsg) {
                     po[so] = h;
@@ -1058,7 +1012,7 @@ __global__ __launch_bounds__(512, NB >= 3 ? 2 : 4) void k_conv3_up_split_s4(UpSp
                 y[j] = fmaf(x[j] - af.x, af.y, af.z);
             }
             h8 h, l;
-            us_split8(y, h, l);
+            rf_split8(y, h, l);
             *reinterpret_cast<h8*>(myslot) = h;
             *reinterpret_cast<h8*>(myslot + U4_A_PLANE) = l;
         };
@@ -1089,7 +1043,7 @@ __global__ __launch_bounds__(512, NB >= 3 ? 2 : 4) void k_conv3_up_split_s4(UpSp
                     const unsigned char* ap = abase + (m >> 1) * (4 * 216 * 16) + zplane[m & 1] + at;
                     const h8 ah = *reinterpret_cast<const h8*>(ap);
                     const h8 al = *reinterpret_cast<const h8*>(ap + U4_A_PLANE);
-                    us_mfma_block<NB>(hi[m], lo[m], ah, al, bh, bl);
+                    rf_split_mfma<NB>(hi[m], lo[m], ah, al, bh, bl);
                 }
 #pragma unroll
                 for (int nb = 0; nb < NB; ++nb) { bh[nb] = nh[nb]; bl[nb] = nl[nb]; }
@@ -1127,7 +1081,7 @@ __global__ __launch_bounds__(512, NB >= 3 ? 2 : 4) void k_conv3_up_split_s4(UpSp
                     y[jj] = fmaf(s1[(size_t)((cb0 + scg) * 8 + jj) * 8] - af.x, af.y, af.z);
                 }
                 h8 h, l;
-                us_split8(y, h, l);
+                rf_split8(y, h, l);
                 *reinterpret_cast<h8*>(myslot) = h;
                 *reinterpret_cast<h8*>(myslot + U4_B_PLANE) = l;
             }
@@ -1144,7 +1098,7 @@ __global__ __launch_bounds__(512, NB >= 3 ? 2 : 4) void k_conv3_up_split_s4(UpSp
                         const unsigned char* p = bbase + cg * 2 * U4_B_PLANE + (m >> 1) * (4 * 64 * 16) + zb[tzp][m & 1];
                         const h8 ah = *reinterpret_cast<const h8*>(p);
                         const h8 al = *reinterpret_cast<const h8*>(p + U4_B_PLANE);
-                        us_mfma_block<NB>(hi[m], lo[m], ah, al, bh, bl);
+                        rf_split_mfma<NB>(hi[m], lo[m], ah, al, bh, bl);
                     }
 #pragma unroll
                     for (int nb = 0; nb < NB; ++nb) { bh[nb] = nh[nb]; bl[nb] = nl[nb]; }
@@ -1167,7 +1121,7 @@ __global__ __launch_bounds__(512, NB >= 3 ? 2 : 4) void k_conv3_up_split_s4(UpSp
                     const int row = 4 * g + r, sm = 4 * (m >> 1) + (row >> 2);
                     const int z = m & 1 ? 2 - pz : 3 * pz;
                     const int lin = sm * 64 + z * 16 + (2 * ((row >> 1) & 1) + py) * 4 + 2 * (row & 1) + px;
-                    e[(nb * 16 + col) * U4_E_STRIDE + lin] = rf_relu(fmaf(lo[m][nb][r], 1.0f / US_LO, hi[m][nb][r]));
+                    e[(nb * 16 + col) * U4_E_STRIDE + lin] = rf_relu(rf_split_join(hi[m][nb][r], lo[m][nb][r]));
                 }
     }
     __syncthreads();
@@ -1243,7 +1197,7 @@ __global__ __launch_bounds__(512, 4) void k_conv3_up_split_box(UpSplitArgs a, in
             yv[j] = in ? fmaf(sp[(size_t)j * hvol] - af.x, af.y, af.z) : 0.f;       // zero padding of the NORMALISED tensor
         }
         h8 h, l;
-        us_split8(yv, h, l);
+        rf_split8(yv, h, l);
         unsigned char* p = lds + cg * 2 * US_B_PLANE + v * 16;
         *reinterpret_cast<h8*>(p) = h;
         *reinterpret_cast<h8*>(p + US_B_PLANE) = l;
@@ -1271,7 +1225,7 @@ __global__ __launch_bounds__(512, 4) void k_conv3_up_split_box(UpSplitArgs a, in
             for (int m = 0; m < 4; ++m) {
                 const h8 ah = *reinterpret_cast<const h8*>(ap + m * US_BZ * 16);
                 const h8 al = *reinterpret_cast<const h8*>(ap + m * US_BZ * 16 + US_B_PLANE);
-                us_mfma_block<NB>(hi[m], lo[m], ah, al, bh, bl);
+                rf_split_mfma<NB>(hi[m], lo[m], ah, al, bh, bl);
             }
         }
     }
@@ -1288,7 +1242,7 @@ __global__ __launch_bounds__(512, 4) void k_conv3_up_split_box(UpSplitArgs a, in
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int lin = (2 * m + pz) * 64 + (2 * yj + py) * 8 + 2 * r + px;
-                    e[(nb * 16 + col) * UB_E_STRIDE + lin] = rf_relu(fmaf(lo[m][nb][r], 1.0f / US_LO, hi[m][nb][r]));
+                    e[(nb * 16 + col) * UB_E_STRIDE + lin] = rf_relu(rf_split_join(hi[m][nb][r], lo[m][nb][r]));
                 }
     }
     __syncthreads();
@@ -1398,7 +1352,7 @@ __global__ __launch_bounds__(512, 4) void k_conv3_up_split_boxp(UpSplitArgs a, i
             yv[j] = xin ? fmaf(xr[j] - af.x, af.y, af.z) : 0.f;                          // zero padding of the NORMALISED tensor
         }
         h8 h, l;
-        us_split8(yv, h, l);
+        rf_split8(yv, h, l);
         unsigned char* p = lds + buf * UP_IMG + scg * 2 * US_B_PLANE + sv * 16;
         *reinterpret_cast<h8*>(p) = h;
         *reinterpret_cast<h8*>(p + US_B_PLANE) = l;
@@ -1441,7 +1395,7 @@ __global__ __launch_bounds__(512, 4) void k_conv3_up_split_boxp(UpSplitArgs a, i
                 for (int m = 0; m < 4; ++m) {
                     const h8 ah = *reinterpret_cast<const h8*>(ap + m * US_BZ * 16);
                     const h8 al = *reinterpret_cast<const h8*>(ap + m * US_BZ * 16 + US_B_PLANE);
-                    us_mfma_block<1>(hi[m], lo[m], ah, al, bh, bl);
+                    rf_split_mfma<1>(hi[m], lo[m], ah, al, bh, bl);
                 }
             }
         if (b + bs < b1 && ((b + bs) >> (3 * lt)) != (b >> (3 * lt))) refresh((b + bs) >> (3 * lt));   // the next box is in another sample (the table was last read before B(b - 1))
@@ -1453,7 +1407,7 @@ __global__ __launch_bounds__(512, 4) void k_conv3_up_split_boxp(UpSplitArgs a, i
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int lin = (2 * m + pz) * 64 + (2 * yj + py) * 8 + 2 * r + px;
-                    e[col * UB_E_STRIDE + lin] = rf_relu(fmaf(lo[m][0][r], 1.0f / US_LO, hi[m][0][r]));
+                    e[col * UB_E_STRIDE + lin] = rf_relu(rf_split_join(hi[m][0][r], lo[m][0][r]));
                 }
         }
         if (b + bs < b1) stage(cur ^ 1);
@@ -1540,7 +1494,7 @@ __global__ __launch_bounds__(512, 2) void k_conv3_up_split_boxskip(UpSplitArgs a
             yv[j] = in ? fmaf(sp[(size_t)j * hvol] - af.x, af.y, af.z) : 0.f;
         }
         h8 h, l;
-        us_split8(yv, h, l);
+        rf_split8(yv, h, l);
         unsigned char* p = lds + UK_B_OFF + cg * 2 * US_B_PLANE + v * 16;
         *reinterpret_cast<h8*>(p) = h;
         *reinterpret_cast<h8*>(p + US_B_PLANE) = l;
@@ -1607,7 +1561,7 @@ __global__ __launch_bounds__(512, 2) void k_conv3_up_split_boxskip(UpSplitArgs a
                 y[j] = vin[r] ? fmaf(x[r][j] - af.x, af.y, af.z) : 0.f;
             }
             h8 h, l;
-            us_split8(y, h, l);
+            rf_split8(y, h, l);
             if (vsl[r] >= 0) {
                 unsigned char* p = lds + UK_A_OFF + vsl[r] * 16;
                 *reinterpret_cast<h8*>(p) = h;
@@ -1626,7 +1580,7 @@ __global__ __launch_bounds__(512, 2) void k_conv3_up_split_boxskip(UpSplitArgs a
             for (int m = 0; m < 4; ++m) {
                 const h8 ah = *reinterpret_cast<const h8*>(ap + m * 2 * US_SZ * 16);
                 const h8 al = *reinterpret_cast<const h8*>(ap + m * 2 * US_SZ * 16 + US_A_PLANE);
-                us_mfma_block<NB>(hi[m], lo[m], ah, al, bh, bl);
+                rf_split_mfma<NB>(hi[m], lo[m], ah, al, bh, bl);
             }
 #pragma unroll
             for (int nb = 0; nb < NB; ++nb) { bh[nb] = nh[nb]; bl[nb] = nl[nb]; }
@@ -1646,7 +1600,7 @@ __global__ __launch_bounds__(512, 2) void k_conv3_up_split_boxskip(UpSplitArgs a
             for (int m = 0; m < 4; ++m) {
                 const h8 ah = *reinterpret_cast<const h8*>(ap + m * US_BZ * 16);
                 const h8 al = *reinterpret_cast<const h8*>(ap + m * US_BZ * 16 + US_B_PLANE);
-                us_mfma_block<NB>(hi[m], lo[m], ah, al, bh, bl);
+                rf_split_mfma<NB>(hi[m], lo[m], ah, al, bh, bl);
             }
 #pragma unroll
             for (int nb = 0; nb < NB; ++nb) { bh[nb] = nh[nb]; bl[nb] = nl[nb]; }
@@ -1665,7 +1619,7 @@ __global__ __launch_bounds__(512, 2) void k_conv3_up_split_boxskip(UpSplitArgs a
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int lin = (2 * m + pz) * 64 + (2 * yj + py) * 8 + 2 * r + px;
-                    e[(nb * 16 + col) * UB_E_STRIDE + lin] = rf_relu(fmaf(lo[m][nb][r], 1.0f / US_LO, hi[m][nb][r]));
+                    e[(nb * 16 + col) * UB_E_STRIDE + lin] = rf_relu(rf_split_join(hi[m][nb][r], lo[m][nb][r]));
                 }
     }
     __syncthreads();
@@ -1739,17 +1693,11 @@ static int up_split_dispatch(UpSplitArgs& a, int c0, int c1, int n, int edge, in
 
 // The persistent form (k_conv3_up_split_pp) takes the pre-split launches with four cout blocks, an even number (>= 4) of skip chunks and enough samples for
 // every CU to walk several: one workgroup per CU (134 KB of LDS, 256 VGPRs), RF_UP_PP_ROUNDS rounds of them (see rf_persistent_wgs on why more than one).
-#ifndef RF_UP_PP
-#define RF_UP_PP 1
-#endif
 #ifndef RF_UP_PP_ROUNDS
 #define RF_UP_PP_ROUNDS 1
 #endif
-#ifndef RF_UP_PP_LINEAR
-#define RF_UP_PP_LINEAR 1                                          // development: 0 = the linear-order entry point stays on k_conv3_up_split
-#endif
 static bool up_split_pp_takes(int c0, int c1, int n, int cout) {
-    return RF_UP_PP && cout > 48 && cout <= 64 && cout % 8 == 0 && c0 >= 32 && c0 % 16 == 0 && c1 >= 8 && c1 % 8 == 0 && c1 <= 8 * US_MAX_CGB && n >= 1024;
+    return cout > 48 && cout <= 64 && cout % 8 == 0 && c0 >= 32 && c0 % 16 == 0 && c1 >= 8 && c1 % 8 == 0 && c1 <= 8 * US_MAX_CGB && n >= 1024;
 }
 
 static int launch_up_split_pp(const UpSplitArgs& a, hipStream_t stream) {
@@ -1823,7 +1771,7 @@ static int up_split_dispatch(UpSplitArgs& a, int c0, int c1, int n, int edge, in
     }
     if (edge == 4) {
         const int nbt = rf_round_up(cout, 16) / 16;
-        if (US_S4_WIDE && (nbt == 4 || nbt == 3)) {
+        if (nbt == 4 || nbt == 3) {
             // all 64 (48: nf = 12) couts in one workgroup (256 VGPRs, 132 KB LDS, one workgroup per CU -- the shape of the 8^3 kernel): the samples are
             // staged and converted ONCE instead of once per 16-cout block
             static RfLdsOptIn opt_wide4, opt_wide3;
@@ -1869,7 +1817,7 @@ extern "C" int rf_conv3d_up_split_presplit(const float* src0, int c0, const floa
     a.src0 = src0; a.src1 = src1; a.affine = reinterpret_cast<const float4*>(gn_affine); a.wp = reinterpret_cast<const h8*>(w_packed);
     a.out = nullptr; a.stats = reinterpret_cast<double2*>(stats); a.c0 = c0; a.c1 = c1; a.n = n; a.cout = cout;
     a.pre_out = reinterpret_cast<h8*>(out_presplit); a.ngamma = next_gamma; a.nbeta = next_beta; a.ngroups = next_groups; a.neps = eps; a.out_ch8 = 0; a.pre_pm = 0;
-    if (RF_UP_PP_LINEAR && up_split_pp_takes(c0, c1, n, cout)) return launch_up_split_pp(a, (hipStream_t)stream);
+    if (up_split_pp_takes(c0, c1, n, cout)) return launch_up_split_pp(a, (hipStream_t)stream);
     return rf_round_up(cout, 16) == 48 ? launch_up_split<3>(a, (hipStream_t)stream) : launch_up_split<4>(a, (hipStream_t)stream);
 }
 

@@ -17,15 +17,13 @@
 // block of 16 x 16 tiles, hi and lo: 12 (10) operand reads per 24 (18) MFMAs.  Partials [GB][cout][cin][27] in fp32 (hi + lo / 2^11), reduced in float64 in a
 // fixed order and rescaled (x 16 / s) by k_wgrad_split_reduce.  Edge >= 8 volumes, cin >= 6; the rest stays with rf_conv3d_k3_wgrad.
 #include "common.h"
-
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+#include "split_operand.h"
 
 namespace {
 constexpr int WS_B_SLOTS = 1440;                            // per plane: 8 channels x 60 halo rows x 3 shifts (4^3: 4 samples x 4 channels x 30 row pairs x 3)
 constexpr int WS_A_STRIDE = 33;                             // slots per cout: 32 rows + 1 (bank spread)
 constexpr int WS_A_SLOTS = 64 * WS_A_STRIDE;                // 2112 per plane
 constexpr int WS_LDS_BYTES = (WS_B_SLOTS + WS_A_SLOTS) * 2 * 16;       // 113,664
-constexpr float WS_ACT_SCALE = 1.0f / 16, WS_LO = 2048.0f;
 constexpr int ws_nc(bool s4) { return s4 ? 4 : 8; }         // input channels per workgroup
 }
 
@@ -38,10 +36,11 @@ struct WgradSplitArgs {
     int cin, cout, n, edge, gb;
 };
 
+// rf_split with a bare v_med3_f32 clamp, which drops a NaN where rf_clamp_f16 keeps it (the backward's NaN behaviour is its own issue)
 __device__ __forceinline__ void ws_split(float v, _Float16& h, _Float16& l) {
     v = __builtin_amdgcn_fmed3f(v, -65504.f, 65504.f);
     h = (_Float16)v;
-    l = (_Float16)fmaf(-WS_LO, (float)h, v * WS_LO);
+    l = (_Float16)fmaf(-SPLIT_LO, (float)h, v * SPLIT_LO);
 }
 
 // S4: whole 4^3 samples, eight per "box", four per half.  A slot is two x-rows of a sample (z, y = 2 yp, 2 yp + 1; 8 contiguous floats of dz); the B image
@@ -110,7 +109,7 @@ __global__ __launch_bounds__(512, 2) void k_conv3_wgrad_split(WgradSplitArgs a) 
                             const float4 v = *reinterpret_cast<const float4*>(a.x + ((size_t)sm * cin + ci) * 64 + (z * 4 + y) * 4);
                             const float raw[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
-                            for (int k = 0; k < 4; ++k) ws_split(fmaf(raw[k] - af.x, af.y, af.z) * WS_ACT_SCALE, h[yy][k + 1], l[yy][k + 1]);
+                            for (int k = 0; k < 4; ++k) ws_split(fmaf(raw[k] - af.x, af.y, af.z) * SPLIT_ACT_SCALE, h[yy][k + 1], l[yy][k + 1]);
                         }
                     }
 #pragma unroll
@@ -136,7 +135,7 @@ __global__ __launch_bounds__(512, 2) void k_conv3_wgrad_split(WgradSplitArgs a) 
                         const float vm = x0 > 0 ? row[-1] : 0.f, vp = x0 + 8 < edge ? row[8] : 0.f;
                         const float raw[10] = {vm, v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w, vp};
 #pragma unroll
-                        for (int k = 0; k < 10; ++k) ws_split(fmaf(raw[k] - af.x, af.y, af.z) * WS_ACT_SCALE, h[k], l[k]);
+                        for (int k = 0; k < 10; ++k) ws_split(fmaf(raw[k] - af.x, af.y, af.z) * SPLIT_ACT_SCALE, h[k], l[k]);
                         if (x0 == 0) { h[0] = (_Float16)0.f; l[0] = (_Float16)0.f; }              // zero padding is of xn, not of x
                         if (x0 + 8 >= edge) { h[9] = (_Float16)0.f; l[9] = (_Float16)0.f; }
                     } else {
@@ -210,7 +209,7 @@ __global__ __launch_bounds__(512, 2) void k_conv3_wgrad_split(WgradSplitArgs a) 
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         const int co = cob + (2 * wm + i) * 16 + kg * 4 + r;
-                        if (co < cout && ci < cin) a.parts[(((size_t)g * cout + co) * cin + ci) * 27 + tap] = fmaf(lo[i][j][r], 1.0f / WS_LO, hi[i][j][r]);
+                        if (co < cout && ci < cin) a.parts[(((size_t)g * cout + co) * cin + ci) * 27 + tap] = rf_split_join(hi[i][j][r], lo[i][j][r]);
                     }
             }
         }
@@ -223,7 +222,7 @@ __global__ __launch_bounds__(512, 2) void k_conv3_wgrad_split(WgradSplitArgs a) 
 __global__ __launch_bounds__(256) void k_wgrad_split_reduce(const float* __restrict__ parts, int gb, size_t count, const float* __restrict__ scales,
                                                             float* __restrict__ dw) {
     __shared__ double red[4][64];
-    const double back = (double)scales[1] / (double)WS_ACT_SCALE;   // 16 / s
+    const double back = (double)scales[1] / (double)SPLIT_ACT_SCALE;   // 16 / s
     const int o = threadIdx.x & 63, sl = threadIdx.x >> 6;
     const size_t i = (size_t)blockIdx.x * 64 + o;
     double s = 0.0;

@@ -1,8 +1,8 @@
-// Shared by the split-operand box kernels (conv3d_split.hip, conv3d_split_zc.hip): the halo-box image in LDS, the operand split and the MFMA triple.
+// Shared by the split-operand box kernels (conv3d_split.hip, conv3d_split_zc.hip): the halo-box image in LDS and the pre-split output.  The operand
+// format itself is split_operand.h.
 #pragma once
 #include "common.h"
-
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+#include "split_operand.h"
 
 namespace {
 // halo box [10][10][10] in 16-byte slots, Y-MAJOR with a padded y stride: slot(z, y, x) = y * 104 + z * 10 + x.  An A operand is a ds_read_b128 of
@@ -15,30 +15,7 @@ constexpr int CS_SY = 104, CS_SZ = 10, CS_VOX = 1000, CS_SLOTS = 1040;
 constexpr int CS_PLANE = CS_SLOTS * 16;                          // bytes of one (h or l) plane
 constexpr int CS_BUF = 2 * CS_PLANE;
 constexpr int CS_LDS_BYTES = 2 * CS_BUF;                         // 66,560
-constexpr float CS_ACT_SCALE = 1.0f / 16, CS_W_SCALE = 16.0f, CS_LO = 2048.0f;
-constexpr bool CS_S4_WIDE = true;
 }   // namespace
-
-
-__device__ __forceinline__ void cs_split8(const float (&y)[8], h8& h, h8& l) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const float v = rf_clamp_f16(y[j] * CS_ACT_SCALE);
-        const _Float16 hh = (_Float16)v;
-        h[j] = hh;
-        l[j] = (_Float16)fmaf(-CS_LO, (float)hh, v * CS_LO);          // (v - h) * 2^11: exact either way, one v_fma_mix instead of cvt + sub + mul
-    }
-}
-
-template <int NB>
-__device__ __forceinline__ void cs_mfma_block(f32x4 (&hi)[NB], f32x4 (&lo)[NB], const h8& ah, const h8& al, const h8 (&bh)[NB], const h8 (&bl)[NB]) {
-#pragma unroll
-    for (int n = 0; n < NB; ++n) hi[n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh[n], hi[n], 0, 0, 0);
-#pragma unroll
-    for (int n = 0; n < NB; ++n) lo[n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl[n], lo[n], 0, 0, 0);
-#pragma unroll
-    for (int n = 0; n < NB; ++n) lo[n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh[n], lo[n], 0, 0, 0);
-}
 
 // pre-split OUTPUT (whole 8^3 samples, 16 couts in one workgroup): the NEXT layer's GroupNorm -- its gamma / beta / groups / eps over this layer's couts --
 // is applied in the epilogue from the sample's own statistics and the result written as that layer's pre-split input; null: off

@@ -10,6 +10,7 @@
 // weight image [K][cout16]; waves are fully independent and latency is hidden by occupancy (8 waves/SIMD).
 // v_mfma_f32_16x16x4_f32 is a k-ordered fp32 FMA chain, so results are plain fp32.
 #include "common.h"
+#include "split_operand.h"
 
 __global__ void k_convv_pack(const float* __restrict__ w, int cout, int cin, int k3, int kpad, int cout16, float* __restrict__ wp) {
     const size_t total = (size_t)kpad * cout16;
@@ -536,18 +537,12 @@ struct ConvVVArgs {
 };
 
 // the column's outputs of one 4-channel group -> bias, LeakyReLU, then the consumer's own scale / clamp / split; lane = consecutive x: 512-byte runs
-typedef _Float16 rf_h4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void convv_store_split(unsigned char* o, size_t plane_bytes, const float (&v)[4]) {
-    rf_h4 hh, ll;
+    h4 hh, ll;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const float t = rf_clamp_f16(v[e] * (1.0f / 16));
-        const _Float16 h = (_Float16)t;
-        hh[e] = h;
-        ll[e] = (_Float16)fmaf(-2048.0f, (float)h, t * 2048.0f);
-    }
-    *reinterpret_cast<rf_h4*>(o) = hh;
-    *reinterpret_cast<rf_h4*>(o + plane_bytes) = ll;
+    for (int e = 0; e < 4; ++e) rf_split_at(v[e] * SPLIT_ACT_SCALE, hh, ll, e);
+    *reinterpret_cast<h4*>(o) = hh;
+    *reinterpret_cast<h4*>(o + plane_bytes) = ll;
 }
 
 typedef float rf_v2 __attribute__((ext_vector_type(2)));

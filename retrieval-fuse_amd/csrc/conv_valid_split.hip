@@ -17,13 +17,10 @@
 // B operands (weights): f16 fragment image from rf_convv_split_pack_weight ([chunk][k-step][n-block][h|l][lane][8 halves]), L2-resident,
 // global -> VGPR one k-step ahead (across chunk boundaries too).
 #include "common.h"
+#include "split_operand.h"
 #include <type_traits>
 
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-
 namespace {
-constexpr float VS_ACT_SCALE = 1.0f / 16, VS_W_SCALE = 16.0f, VS_LO = 2048.0f;
 constexpr int VS_NT = 256, VS_MB = 4, VS_M = 256;               // threads, m-blocks per wave, output voxels per tile
 constexpr int VS_EV = VS_M + 4;                                 // floats per cout row of the epilogue tile
 constexpr size_t VS_LDS_MAX = 78 * 1024;                        // two workgroups per CU
@@ -149,10 +146,9 @@ __global__ void k_convv_split_pack(const float* __restrict__ w, int cout, int ci
                 const int tap = p / cgc, ci = (chunk * cgc + p % cgc) * 4 + (j & 3);
                 v = (double)w[((size_t)co * cin + ci) * k3 + tap];
             }
-            v *= (double)VS_W_SCALE;
-            v = v > 65504.0 ? 65504.0 : (v < -65504.0 ? -65504.0 : v);
-            const _Float16 h = (_Float16)(float)v;
-            out[j] = part == 0 ? h : (_Float16)(float)((v - (double)(float)h) * (double)VS_LO);
+            _Float16 h, l;
+            rf_split_weight(v, h, l);
+            out[j] = part == 0 ? h : l;
         }
         wp[i] = out;
     }
@@ -302,15 +298,10 @@ __global__ __launch_bounds__(VS_NT, WPE) void k_convv_split(ConvVSArgs a) {
                         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                         for (int b = 0; b < SB; ++b) {
-                            const float sc = (!RAGGED || ((real >> b) & 1u)) ? VS_ACT_SCALE : 0.f;
+                            const float sc = (!RAGGED || ((real >> b) & 1u)) ? SPLIT_ACT_SCALE : 0.f;
                             h4 hh, ll;
 #pragma unroll
-                            for (int e = 0; e < 4; ++e) {
-                                const float t = rf_clamp_f16(v[b][e] * sc);
-                                const _Float16 h = (_Float16)t;
-                                hh[e] = h;
-                                ll[e] = (_Float16)fmaf(-VS_LO, (float)h, t * VS_LO);     // (t - h) * 2^11, exact either way; one v_fma_mix_f32
-                            }
+                            for (int e = 0; e < 4; ++e) rf_split_at(v[b][e] * sc, hh, ll, e);
                             const int idx = i + b * NT;
                             *reinterpret_cast<h4*>(lds + idx * 8) = hh;
                             *reinterpret_cast<h4*>(lds + plane + idx * 8) = ll;
@@ -360,7 +351,6 @@ __global__ __launch_bounds__(VS_NT, WPE) void k_convv_split(ConvVSArgs a) {
 
     // ---- epilogue: hi + lo / 2^11 (activation and weight scales cancel), bias, LeakyReLU; through LDS so that the stores are long
     // contiguous runs -- per cout block the 4 waves each stream four cout rows out, lane = consecutive voxel of the tile
-    static_assert(VS_ACT_SCALE * VS_W_SCALE == 1.0f, "epilogue assumes the operand scales cancel");
     float* eb = reinterpret_cast<float*>(lds);                      // [16][VS_EV]
     const size_t ovol = (size_t)so * so * so;
     int zlim = so - z0;
@@ -379,7 +369,7 @@ __global__ __launch_bounds__(VS_NT, WPE) void k_convv_split(ConvVSArgs a) {
             f32x4 v;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const float t = fmaf(lo[mb][nb][r], 1.0f / VS_LO, hi[mb][nb][r]) + bz[nb];
+                const float t = rf_split_join(hi[mb][nb][r], lo[mb][nb][r]) + bz[nb];
                 v[r] = t > 0.f ? t : t * a.slope;
             }
             *reinterpret_cast<f32x4*>(eb + j * VS_EV + (wave * MB + mb) * 16 + g * 4) = v;
@@ -396,11 +386,11 @@ __global__ __launch_bounds__(VS_NT, WPE) void k_convv_split(ConvVSArgs a) {
                     if (eoff[i] >= 0) {
                         h4 hh, ll;
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            const float t = rf_clamp_f16(eb[(wave * 4 + e) * VS_EV + lane + 64 * i] * VS_ACT_SCALE);
+                        for (int e = 0; e < 4; ++e) {          // rf_split_at written out: the helper reorders this kernel's code (-24 instructions)
+                            const float t = rf_clamp_f16(eb[(wave * 4 + e) * VS_EV + lane + 64 * i] * SPLIT_ACT_SCALE);
                             const _Float16 h = (_Float16)t;
                             hh[e] = h;
-                            ll[e] = (_Float16)fmaf(-VS_LO, (float)h, t * VS_LO);
+                            ll[e] = (_Float16)fmaf(-SPLIT_LO, (float)h, t * SPLIT_LO);
                         }
                         *reinterpret_cast<h4*>(o + (size_t)eoff[i] * 8) = hh;
                         *reinterpret_cast<h4*>(o + (ovol + (size_t)eoff[i]) * 8) = ll;

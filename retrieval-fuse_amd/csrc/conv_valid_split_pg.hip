@@ -21,17 +21,15 @@
 //       whose voxel lies outside the volume (ragged last tiles) or whose channel group is padding gets an out-of-range offset -- no branch.
 // Split form in and out only (rf_conv3d_valid_leaky_split_ex's in_split = out_split = 1: the layer sits between two layers that read / write it).
 #include "common.h"
+#include "split_operand.h"
 #include <type_traits>
 
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 namespace {
-constexpr float PG_ACT_SCALE = 1.0f / 16, PG_W_SCALE = 16.0f, PG_LO = 2048.0f;
 constexpr int PG_NT = 512, PG_TT = 256, PG_MB = 2;               // threads, threads of a team, 32-voxel m-blocks per wave, output voxels per tile (of a team)
 constexpr int PG_SB = 4;                                        // staged items (4 channels of TWO voxels along x: 16 bytes of the h plane, 16 of the l plane) per thread and tile
 constexpr size_t PG_LDS_MAX = 160 * 1024;
@@ -119,10 +117,9 @@ __global__ void k_convv_pg_pack(ConvPGArgs a, const float* __restrict__ w, h8* _
             const int p = 4 * q + 2 * hk + (j >> 2);
             double v = 0.0;
             if (p < k3 * cg && co < cout) v = (double)w[((size_t)co * cin + (p % cg) * 4 + (j & 3)) * k3 + p / cg];
-            v *= (double)PG_W_SCALE;
-            v = v > 65504.0 ? 65504.0 : (v < -65504.0 ? -65504.0 : v);
-            const _Float16 h = (_Float16)(float)v;
-            out[j] = part == 0 ? h : (_Float16)(float)((v - (double)(float)h) * (double)PG_LO);
+            _Float16 h, l;
+            rf_split_weight(v, h, l);
+            out[j] = part == 0 ? h : l;
         }
         wp[i] = out;
     }
@@ -280,7 +277,7 @@ __global__ __launch_bounds__(PG_NT, 1) void k_convv_split_pg(ConvPGArgs a) {
         const h8* wg = a.wp + a.hdr / 4;
         h8* wd = reinterpret_cast<h8*>(lds);
         for (int i = tid; i < KS * 2 * 64; i += PG_NT) wd[i] = wg[i];
-        if (tid < 32) bzt[tid] = (a.bias && tid < a.cout) ? a.bias[tid] * PG_ACT_SCALE : 0.f;
+        if (tid < 32) bzt[tid] = (a.bias && tid < a.cout) ? a.bias[tid] * SPLIT_ACT_SCALE : 0.f;
         uint2* zb = reinterpret_cast<uint2*>(bzt + 32);               // the images' padding is never read, the dump slots are never read: tidy all the same
         for (int i = tid; i < 4 * plane / 8; i += PG_NT) zb[i] = make_uint2(0u, 0u);
         __syncthreads();
@@ -367,7 +364,6 @@ __global__ __launch_bounds__(PG_NT, 1) void k_convv_split_pg(ConvPGArgs a) {
         const PgTile nn2 = walk_tile();
         if (!PG_ABL(2)) request(nn2, ph, pl);                  // (behind the last tile: the last tile again -- harmless, no branch)
         PG_STAMP(3);
-        static_assert(PG_ACT_SCALE * PG_W_SCALE == 1.0f, "epilogue assumes the operand scales cancel");
         if (!PG_ABL(1) || hi[0][0] == 123.456f) {
             // accumulator register r of a lane: cout 8 (r / 4) + 4 hk + (r & 3) of its voxel = channel group 2 (r / 4) + hk: rq < NRQ real groups (the couts padded to
             // 32 are whole registers here: never touched)
@@ -393,21 +389,21 @@ __global__ __launch_bounds__(PG_NT, 1) void k_convv_split_pg(ConvPGArgs a) {
                     for (int rq = 0; rq < NRQ; ++rq) {
                         const int grp = 2 * rq + hk;
                         // hi + lo / 2^11 + bias, LeakyReLU, the consumer's 1 / 16, clamp, split -- on register PAIRS (v_pk_*_f32); the 1 / 16 is applied first:
-                        // exact, every later step scales with it
+                        // exact, every later step scales with it.  Kept local: rf_split_at works on single values, this form on pairs
                         h4 hh, ll;
 #pragma unroll
                         for (int r = 0; r < 4; r += 2) {
                             const f32x2 h2 = {hi[mb][4 * rq + r], hi[mb][4 * rq + r + 1]}, l2 = {lo[mb][4 * rq + r], lo[mb][4 * rq + r + 1]}, b2 = {bz_[rq][r], bz_[rq][r + 1]};
-                            const f32x2 t0 = __builtin_elementwise_fma(l2, (f32x2){PG_ACT_SCALE / PG_LO, PG_ACT_SCALE / PG_LO}, h2 * (f32x2){PG_ACT_SCALE, PG_ACT_SCALE}) + b2;
+                            const f32x2 t0 = __builtin_elementwise_fma(l2, (f32x2){SPLIT_ACT_SCALE / SPLIT_LO, SPLIT_ACT_SCALE / SPLIT_LO}, h2 * (f32x2){SPLIT_ACT_SCALE, SPLIT_ACT_SCALE}) + b2;
                             const f32x2 ts = t0 * (f32x2){a.slope, a.slope};
                             f32x2 t;
                             t.x = rf_clamp_f16(rf_max(t0.x, ts.x));
                             t.y = rf_clamp_f16(rf_max(t0.y, ts.y));
-                            const f32x2 tl = t * (f32x2){PG_LO, PG_LO};
+                            const f32x2 tl = t * (f32x2){SPLIT_LO, SPLIT_LO};
                             const _Float16 ha = (_Float16)t.x, hb = (_Float16)t.y;
                             hh[r] = ha; hh[r + 1] = hb;
-                            ll[r] = (_Float16)fmaf(-PG_LO, (float)ha, tl.x);
-                            ll[r + 1] = (_Float16)fmaf(-PG_LO, (float)hb, tl.y);
+                            ll[r] = (_Float16)fmaf(-SPLIT_LO, (float)ha, tl.x);
+                            ll[r + 1] = (_Float16)fmaf(-SPLIT_LO, (float)hb, tl.y);
                         }
                         unsigned vo = (unsigned)grp * 2u * lsoff + vox;
                         if (!INTERIOR) vo = (vin && grp * 4 < a.cout) ? vo : 0xfffffff0u;

@@ -323,7 +323,7 @@ def conv3d_up_gn_relu(src0, src1, aff, w_up_packed, cout):
 CONV_ARITH = 'split'
 
 # ---- value range of the split-operand (f16 x f16) forms.  They carry activations scaled by 2^-4 and weights scaled by 2^4 as pairs of f16 values
-# (csrc/conv3d_split.hip:20-24): |GroupNorm output| above 65504 * 16 or a (pre-summed) weight above 65504 / 16 would CLAMP where the reference
+# (csrc/split_operand.h): |GroupNorm output| above 65504 * 16 or a (pre-summed) weight above 65504 / 16 would CLAMP where the reference
 # computes in fp32 range.  Both are decidable from the parameters alone, once per parameter version:
 #   weights      max |w| <= SPLIT_MAX_ABS_WEIGHT (the decoder form adds up to 8 taps before it splits: 65504 / 16 / 8);
 #   activations  a GroupNorm output is (x - mean) * rstd * gamma + beta with |x - mean| * rstd <= sqrt(elements of the group), so

@@ -81,3 +81,21 @@ def fixture_problem(fix, shapes_by_module):
     digest = sha(*[v.numpy() for m in ('unet_backbone', 'decoder', 'retrieval_backbone', 'patched_attention_block') for v in sds[m].values()])
     assert digest == str(fix['weights_sha']), 'state_dict key order / shapes differ from the reference modules'
     return cfg, x_in, retr, sds
+
+
+def to_split_acts(ops, x):
+    """fp32 [n, c, s, s, s] -> ops.SplitActs, the split-operand format of retrieval-fuse_amd/csrc/split_operand.h as include/rfuse.h lays it out:
+    [n][c/4][h | l][voxel][4 halves], h = f16(x/16), l = f16((x/16 - h) * 2^11)"""
+    n, c, s = x.shape[0], x.shape[1], x.shape[2]
+    t = (x * (1.0 / 16)).clamp(-65504.0, 65504.0)
+    h = t.half()
+    l = ((t - h.float()) * 2048.0).half()
+    hl = torch.stack([h, l], 0).view(2, n, c // 4, 4, s * s * s).permute(1, 2, 0, 4, 3).contiguous()
+    return ops.SplitActs(hl.view(torch.float32).view(n, c, s, s, s))
+
+
+def from_split_acts(xs):
+    """ops.SplitActs -> the fp32 [n, c, s, s, s] values it stands for: (h + l / 2^11) * 16"""
+    n, c, s = xs.shape[0], xs.shape[1], xs.shape[2]
+    hl = xs.data.view(torch.float16).view(n, c // 4, 2, s * s * s, 4).float()
+    return ((hl[:, :, 0] + hl[:, :, 1] * (1.0 / 2048.0)) * 16.0).permute(0, 1, 3, 2).reshape(n, c, s, s, s)

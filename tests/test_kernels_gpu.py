@@ -5,6 +5,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import helpers
 from oracle import refpath
 
 pytestmark = pytest.mark.gpu
@@ -1120,22 +1121,6 @@ def test_split_form_between_the_encoder_layers_changes_no_bit(ops, enc):
     assert torch.equal(res[True][0], res[False][0]) and torch.equal(res[True][1], res[False][1])
 
 
-def _to_split(ops, x):
-    """fp32 [n, c, s, s, s] -> ops.SplitActs as include/rfuse.h defines it: [n][c/4][h | l][voxel][4 halves], h = f16(x/16), l = f16((x/16 - h) * 2^11)"""
-    n, c, s = x.shape[0], x.shape[1], x.shape[2]
-    t = (x * (1.0 / 16)).clamp(-65504.0, 65504.0)
-    h = t.half()
-    l = ((t - h.float()) * 2048.0).half()
-    hl = torch.stack([h, l], 0).view(2, n, c // 4, 4, s * s * s).permute(1, 2, 0, 4, 3).contiguous()
-    return ops.SplitActs(hl.view(torch.float32).view(n, c, s, s, s))
-
-
-def _from_split(xs):
-    n, c, s = xs.shape[0], xs.shape[1], xs.shape[2]
-    hl = xs.data.view(torch.float16).view(n, c // 4, 2, s * s * s, 4).float()
-    return ((hl[:, :, 0] + hl[:, :, 1] * (1.0 / 2048.0)) * 16.0).permute(0, 1, 3, 2).reshape(n, c, s, s, s)
-
-
 @pytest.mark.parametrize('spec', [(2, 70, 24), (1, 92, 24), (1, 140, 24), (3, 64, 20), (1, 66, 24)])
 def test_conv3d_valid_leaky_split_pg(ops, spec):
     """the persistent two-team form of PCPatch48's 12 -> 24 k3 layer on a whole padded chunk (model/retrieval.py:222 of the reference evaluated fully
@@ -1146,19 +1131,19 @@ def test_conv3d_valid_leaky_split_pg(ops, spec):
     cin, k = 12, 3
     gen = torch.Generator().manual_seed(sum(spec) + 6)
     x, w, b = rnd(gen, n, cin, s, s, s), rnd(gen, cout, cin, k, k, k, scale=1 / np.sqrt(cin * k ** 3)), rnd(gen, cout)
-    xs = _to_split(ops, x.to(DEV))
+    xs = helpers.to_split_acts(ops, x.to(DEV))
     assert ops.conv_valid_split_pg_supported((n, cin, s), cout, k, 1)
     got = ops.conv3d_valid_leaky_split_pg(xs, ops.pack_convv_split_pg_weight(w.to(DEV), s, 1), b.to(DEV), cout, k, 1, 0.2)
     assert isinstance(got, ops.SplitActs) and tuple(got.shape) == (n, cout, s - 2, s - 2, s - 2)
-    ref = F.leaky_relu(F.conv3d(_from_split(xs).double().cpu(), w.double(), b.double()), 0.2)
-    err = (_from_split(got).double().cpu() - ref).abs()
+    ref = F.leaky_relu(F.conv3d(helpers.from_split_acts(xs).double().cpu(), w.double(), b.double()), 0.2)
+    err = (helpers.from_split_acts(got).double().cpu() - ref).abs()
     print(f'valid split pg {spec}: rms {err.pow(2).mean().sqrt():.3e} max {err.max():.3e}')
     assert err.max() <= 1e-5
     if cout % 4 == 0 and ops.conv_valid_split_supported(x.to(DEV), cout, k, 1):
         v1 = ops.conv3d_valid_leaky_split(xs, ops.pack_convv_split_weight(w.to(DEV), s, 1), b.to(DEV), cout, k, 1, 0.2, out_split=True)
-        e1 = (_from_split(v1).double().cpu() - ref).abs()
+        e1 = (helpers.from_split_acts(v1).double().cpu() - ref).abs()
         assert err.pow(2).mean().sqrt() <= 1.05 * e1.pow(2).mean().sqrt() and err.max() <= 1.25 * e1.max()
-        assert (_from_split(v1) - _from_split(got)).abs().max() <= 4e-6
+        assert (helpers.from_split_acts(v1) - helpers.from_split_acts(got)).abs().max() <= 4e-6
 
 
 def test_conv3d_valid_leaky_split_pg_refuses_what_it_was_not_built_for(ops):
@@ -1170,7 +1155,7 @@ def test_conv3d_valid_leaky_split_pg_refuses_what_it_was_not_built_for(ops):
     w, b = rnd(gen, 24, 12, 3, 3, 3).to(DEV), rnd(gen, 24).to(DEV)
     with pytest.raises(ValueError):
         ops.pack_convv_split_pg_weight(w, 141, 1)
-    xs = _to_split(ops, rnd(gen, 1, 12, 64, 64, 64).to(DEV))
+    xs = helpers.to_split_acts(ops, rnd(gen, 1, 12, 64, 64, 64).to(DEV))
     wp = ops.pack_convv_split_pg_weight(w, 64, 1)
     with pytest.raises(RuntimeError, match='slope'):
         ops.conv3d_valid_leaky_split_pg(xs, wp, b, 24, 3, 1, 1.5)

@@ -7,7 +7,7 @@ REPO = Path(__file__).resolve().parents[1]
 CSRC = REPO / 'retrieval-fuse_amd' / 'csrc'
 OUT = REPO / 'tools' / '_haz'
 VARIANTS = {'base': [], 'nostage': ['-DRF_PP_ABL=1'], 'noepi': ['-DRF_PP_ABL=2'], 'noweights': ['-DRF_PP_ABL=4'], 'nomfma': ['-DRF_PP_ABL=8'],
-            'nostage_noepi': ['-DRF_PP_ABL=3'], 'mfma_only': ['-DRF_PP_ABL=7'], 'old': ['-DRF_UP_PP=0']}
+            'nostage_noepi': ['-DRF_PP_ABL=3'], 'mfma_only': ['-DRF_PP_ABL=7']}
 if len(sys.argv) > 1 and sys.argv[1] == 'build':
     sys.path.insert(0, str(CSRC))
     import build
@@ -25,6 +25,6 @@ n = sys.argv[1] if len(sys.argv) > 1 else '8192'
 for rnd in range(2):
     for tag in VARIANTS:
         env = dict(os.environ, RFUSE_LIB=str(OUT / ('libabl_%s.so' % tag)))
-        r = subprocess.run([sys.executable, str(REPO / 'tools' / 'pp_bench.py'), n] + ([] if tag == 'old' else ['--pm']), env=env, capture_output=True, text=True)
+        r = subprocess.run([sys.executable, str(REPO / 'tools' / 'pp_bench.py'), n, '--pm'], env=env, capture_output=True, text=True)
         line = [l for l in r.stdout.splitlines() if l.startswith('n=')]
         print('%-14s %s' % (tag, line[0] if line else r.stderr[-300:]))

@@ -1,5 +1,5 @@
 """Dev tool (GPU box): the dominant launch alone -- rf_conv3d_up_split_presplit, 32+64 -> 56 @8^3 x 8192 (reference model/refinement.py:64-73, dec1 conv1) --
-HIP events, whichever kernel the library in RFUSE_LIB dispatches (k_conv3_up_split_pp, or k_conv3_up_split<4> when built with -DRF_UP_PP=0), and the
+HIP events, with the library in RFUSE_LIB (its k_conv3_up_split_pp), and the
 maximum difference of the pre-split bytes from a reference library's (RFUSE_REF_OUT: a .pt file written by a previous run with --save).
   python tools/pp_bench.py [n=8192] [--pm] [--save file] [--cmp file]      (--pm: the parity-major entry point)"""
 import sys
