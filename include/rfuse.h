@@ -571,6 +571,25 @@ int rf_mc_emit(const float* sdf, int x, int y, int z, float level, const signed 
 int rf_paste_chunks(const float* df, int b, const int* sel, const long long* dst, int m, long long sx, long long sy, int round_half, double* flat,
                     void* stream);
 
+/* ------------------------------------------------------------------------------- evaluation metrics (csrc/metrics.hip) */
+
+/* The exact quantities behind the reference's IoU / Chamfer3D / Precision / Recall (util/metrics.py:6-89, imported by
+ * trainer/train_refinement.py:16 and util/retrieval.py; computed per validation batch at trainer/train_refinement.py:122-146,223-227 and per scene at
+ * util/retrieval.py:167-175).  Chamfer3D's brute-force nearest-neighbour search over torch.nonzero points (util/metrics.py:42-49, the un-vendored
+ * chamfer_3DDist) becomes a squared Euclidean distance transform on the integer voxel grid.
+ * EXCEPTION to the cubic power-of-two convention above: volumes are [b][1][d][h][w] (w innermost, contiguous) with ANY edges 1..2048 (else
+ * RF_E_UNSUPPORTED, as for a batch one of whose launches would need 2^24 workgroups or more).  Each input is an occupancy grid (kind RF_OCC_GRID: bool / uint8, non-zero = occupied) or a distance field with threshold thr
+ * (RF_OCC_DF_F32 / RF_OCC_DF_F16: occupied iff df <= thr; the caller rounds thr to the field's precision first, as torch's `df <= scalar` does; NaN is
+ * unoccupied).  out [b][5] int64 per volume: n_pred, n_target, n_inter, s_tp = sum_{t in T} min_{p in P} |t - p|^2, s_pt = sum_{p in P} min_{t in T}
+ * |p - t|^2 (squared voxel-index units, exact; both 0 when either grid is empty, and when chamfer == 0).  Integer arithmetic only: the same bits on
+ * every run.  ws: rf_occupancy_stats_ws_bytes(b, d, h, w, chamfer) bytes (0 for an unsupported shape). */
+#define RF_OCC_GRID 0
+#define RF_OCC_DF_F32 1
+#define RF_OCC_DF_F16 2
+size_t rf_occupancy_stats_ws_bytes(int b, int d, int h, int w, int chamfer);
+int rf_occupancy_stats(const void* pred, int pred_kind, float pred_thr, const void* target, int target_kind, float target_thr, int b, int d, int h,
+                       int w, int chamfer, int64_t* out, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

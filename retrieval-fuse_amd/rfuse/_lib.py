@@ -164,6 +164,8 @@ SIGNATURES = {
     'rf_gather_patches_f16': (c_i, [c_p, c_i64, c_p, c_i, c_i, c_f, c_f, c_f, c_f, c_i, c_fp, c_p]),
     'rf_compose_overlap': (c_i, [c_p, c_i, c_i64, c_fp, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_fp, c_fp, c_p]),
     'rf_paste_chunks': (c_i, [c_fp, c_i, c_p, c_p, c_i, c_i64, c_i64, c_i, c_p, c_p]),
+    'rf_occupancy_stats_ws_bytes': (c_sz, [c_i, c_i, c_i, c_i, c_i]),
+    'rf_occupancy_stats': (c_i, [c_p, c_i, c_f, c_p, c_i, c_f, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_sz, c_p]),
 }
 
 _lib = None
