@@ -1,188 +1,98 @@
 """ctypes binding of librfuse_hip.so (the C ABI declared in include/rfuse.h).
 
-There is NO fallback: if the library is missing or a call fails, a RuntimeError is raised.  ``import torch`` must come
+The argument and return types are read from the header itself at import (``parse_header``): there is no second copy of the ABI to keep
+in step.  There is NO fallback: if the library is missing a RuntimeError is raised, and every entry point that returns a status
+(``is_status``) raises a RuntimeError with ``rf_last_error()`` when that status is not 0.  ``import torch`` must come
 first so that the HIP runtime the library binds to is the one PyTorch-ROCm already loaded (same SONAME).
 """
 import ctypes
 import os
+import re
 from pathlib import Path
 
 import torch  # noqa: F401  (loads libamdhip64 before we dlopen)
 
 _HERE = Path(__file__).resolve().parent
 LIB_PATH = Path(os.environ.get('RFUSE_LIB', _HERE / 'librfuse_hip.so'))
+HEADER_PATH = _HERE.parents[1] / 'include' / 'rfuse.h'
 
-c_fp = ctypes.c_void_p     # device float*
-c_p = ctypes.c_void_p
-c_i = ctypes.c_int
-c_f = ctypes.c_float
-c_sz = ctypes.c_size_t
-c_i64 = ctypes.c_int64
+# every scalar type include/rfuse.h uses; any pointer is a c_void_p, and `const char*` as a return type a c_char_p
+_SCALARS = {'int': ctypes.c_int, 'float': ctypes.c_float, 'size_t': ctypes.c_size_t, 'int64_t': ctypes.c_int64, 'long long': ctypes.c_int64}
 
-# name -> (restype, argtypes); one entry per symbol declared in include/rfuse.h
-SIGNATURES = {
-    'rf_abi_version': (c_i, []),
-    'rf_last_error': (ctypes.c_char_p, []),
-    'rf_conv3_pack_weight': (c_i, [c_fp, c_i, c_i, c_fp, c_p]),
-    'rf_conv3_packed_floats': (c_sz, [c_i, c_i]),
-    'rf_gn_stats': (c_i, [c_fp, c_i, c_fp, c_i, c_i, c_i, c_fp, c_fp, c_i, c_f, c_fp, c_p, c_sz, c_p]),
-    'rf_gn_stats_ws_bytes': (c_sz, [c_i, c_i]),
-    'rf_conv3d_k3_gn_relu': (c_i, [c_fp, c_i, c_fp, c_i, c_i, c_i, c_fp, c_fp, c_i, c_fp, c_p]),
-    'rf_conv3d_k3_gn_relu_stats': (c_i, [c_fp, c_i, c_fp, c_i, c_i, c_i, c_fp, c_fp, c_i, c_fp, c_p, c_p]),
-    'rf_conv3d_stats_tiles': (c_i, [c_i, c_i, c_i, c_i, c_i]),
-    'rf_gn_from_stats': (c_i, [c_p, c_i, c_i, c_p, c_i, c_i, c_i, c_i, c_fp, c_fp, c_i, c_f, c_fp, c_p]),
-    'rf_maxpool3d_2_stats': (c_i, [c_fp, c_i, c_i, c_i, c_fp, c_p, c_p]),
-    'rf_maxpool_stats_tiles': (c_i, [c_i]),
-    'rf_conv3d_k3_gn_relu_direct': (c_i, [c_fp, c_i, c_fp, c_i, c_i, c_i, c_fp, c_fp, c_i, c_fp, c_p]),
-    'rf_maxpool3d_2': (c_i, [c_fp, c_i, c_i, c_i, c_fp, c_p]),
-    'rf_conv1x1_tanh': (c_i, [c_fp, c_i, c_i, c_sz, c_fp, c_fp, c_f, c_f, c_fp, c_p]),
-    'rf_conv3d_valid_leaky': (c_i, [c_fp, c_i, c_i, c_i, c_fp, c_fp, c_i, c_i, c_i, c_f, c_fp, c_p]),
-    'rf_conv3d_valid_leaky_mfma': (c_i, [c_fp, c_i, c_i, c_i, c_fp, c_fp, c_i, c_i, c_i, c_f, c_fp, c_p]),
-    'rf_convv_pack_weight': (c_i, [c_fp, c_i, c_i, c_i, c_fp, c_p]),
-    'rf_convv_packed_floats': (c_sz, [c_i, c_i, c_i]),
-    'rf_conv3d_valid_lds_supported': (c_i, [c_i, c_i, c_i, c_i, c_i, c_i]),
-    'rf_conv3d_valid_leaky_lds': (c_i, [c_fp, c_i, c_i, c_i, c_fp, c_fp, c_i, c_i, c_i, c_f, c_fp, c_p]),
-    'rf_conv3d_valid_valu_supported': (c_i, [c_i, c_i, c_i, c_i, c_i, c_i]),
-    'rf_conv3d_valid_leaky_valu': (c_i, [c_fp, c_i, c_i, c_i, c_fp, c_fp, c_i, c_i, c_i, c_f, c_fp, c_p]),
-    'rf_conv3d_valid_leaky_valu_ex': (c_i, [c_fp, c_i, c_i, c_i, c_fp, c_fp, c_i, c_i, c_i, c_f, c_p, c_i, c_p]),
-    'rf_convv_lds_pack_weight': (c_i, [c_fp, c_i, c_i, c_i, c_fp, c_p]),
-    'rf_convv_lds_packed_floats': (c_sz, [c_i, c_i, c_i]),
-    'rf_conv3d_valid_split_supported': (c_i, [c_i, c_i, c_i, c_i, c_i, c_i]),
-    'rf_conv3d_valid_leaky_split': (c_i, [c_fp, c_i, c_i, c_i, c_p, c_fp, c_i, c_i, c_i, c_f, c_fp, c_p]),
-    'rf_conv3d_valid_leaky_split_ex': (c_i, [c_p, c_i, c_i, c_i, c_i, c_p, c_fp, c_i, c_i, c_i, c_f, c_p, c_i, c_p]),
-    'rf_convv_split_pack_weight': (c_i, [c_fp, c_i, c_i, c_i, c_i, c_i, c_p, c_p]),
-    'rf_convv_split_packed_bytes': (c_sz, [c_i, c_i, c_i, c_i, c_i]),
-    'rf_conv3d_valid_split_pg_supported': (c_i, [c_i, c_i, c_i, c_i, c_i, c_i]),
-    'rf_conv3d_valid_leaky_split_pg': (c_i, [c_p, c_i, c_i, c_i, c_p, c_fp, c_i, c_i, c_i, c_f, c_p, c_p]),
-    'rf_convv_split_pg_pack_weight': (c_i, [c_fp, c_i, c_i, c_i, c_i, c_i, c_p, c_p]),
-    'rf_convv_split_pg_packed_bytes': (c_sz, [c_i, c_i, c_i, c_i, c_i]),
-    'rf_conv3d_pool_supported': (c_i, [c_i, c_i, c_i, c_i, c_i]),
-    'rf_conv3d_k3_gn_relu_pool': (c_i, [c_fp, c_i, c_fp, c_i, c_i, c_i, c_fp, c_fp, c_i, c_fp, c_p, c_fp, c_p, c_p]),
-    'rf_conv3_up_packed_floats': (c_sz, [c_i, c_i, c_i]),
-    'rf_conv3_up_pack_weight': (c_i, [c_fp, c_i, c_i, c_i, c_fp, c_p]),
-    'rf_conv3d_up_supported': (c_i, [c_i, c_i, c_i, c_i, c_i]),
-    'rf_conv3d_up_stats_tiles': (c_i, [c_i, c_i, c_i, c_i, c_i]),
-    'rf_conv3d_up_variant': (c_i, [c_i, c_i, c_i, c_i, c_i]),
-    'rf_conv3d_up_k3_gn_relu': (c_i, [c_fp, c_i, c_fp, c_i, c_i, c_i, c_fp, c_fp, c_i, c_fp, c_p, c_p]),
-    'rf_conv3_split_packed_bytes': (c_sz, [c_i, c_i]),
-    'rf_conv3_split_pack_weight': (c_i, [c_fp, c_i, c_i, c_p, c_p]),
-    'rf_conv3d_split_supported': (c_i, [c_i, c_i, c_i, c_i, c_i]),
-    'rf_conv3d_split_k3_gn_relu': (c_i, [c_fp, c_i, c_i, c_i, c_fp, c_p, c_i, c_fp, c_p, c_fp, c_p, c_p]),
-    'rf_conv3_e2_split_packed_bytes': (c_sz, [c_i, c_i, c_i]),
-    'rf_conv3_e2_split_pack_weight': (c_i, [c_fp, c_i, c_i, c_i, c_p, c_p]),
-    'rf_conv3d_e2_split_supported': (c_i, [c_i, c_i, c_i, c_i]),
-    'rf_conv3d_e2_split_k3_gn_relu': (c_i, [c_fp, c_i, c_i, c_i, c_fp, c_p, c_i, c_fp, c_p, c_p]),
-    'rf_split_act_bytes': (c_sz, [c_i, c_i, c_i]),
-    'rf_conv3d_cin1_presplit_supported': (c_i, [c_i, c_i, c_i, c_i]),
-    'rf_conv3d_cin1_presplit': (c_i, [c_fp, c_i, c_i, c_fp, c_fp, c_f, c_fp, c_i, c_fp, c_fp, c_i, c_f, c_p, c_p]),
-    'rf_conv3d_split_pointwise_supported': (c_i, [c_i, c_i, c_i, c_i]),
-    'rf_conv3d_split_k3_gn_relu_pointwise_tanh': (c_i, [c_fp, c_i, c_i, c_i, c_fp, c_p, c_i, c_fp, c_fp, c_f, c_f, c_fp, c_p]),
-    'rf_conv3d_split_presplit_supported': (c_i, [c_i, c_i, c_i, c_i, c_i]),
-    'rf_conv3d_split_presplit': (c_i, [c_fp, c_i, c_i, c_i, c_fp, c_p, c_i, c_fp, c_fp, c_i, c_f, c_p, c_p, c_p]),
-    'rf_conv3d_up_split_presplit_supported': (c_i, [c_i, c_i, c_i, c_i, c_i, c_i]),
-    'rf_conv3d_up_split_presplit': (c_i, [c_fp, c_i, c_fp, c_i, c_i, c_i, c_fp, c_p, c_i, c_fp, c_fp, c_i, c_f, c_p, c_p, c_p]),
-    'rf_conv3d_split_pre_supported': (c_i, [c_i, c_i, c_i, c_i]),
-    'rf_conv3d_split_pre_stats_tiles': (c_i, [c_i, c_i, c_i, c_i]),
-    'rf_conv3d_split_pre_k3_relu': (c_i, [c_p, c_i, c_i, c_i, c_p, c_i, c_fp, c_p, c_fp, c_p, c_p]),
-    'rf_conv3d_up_split_presplit_pm_supported': (c_i, [c_i, c_i, c_i, c_i, c_i, c_i]),
-    'rf_conv3d_up_split_presplit_pm': (c_i, [c_fp, c_i, c_fp, c_i, c_i, c_i, c_fp, c_p, c_i, c_fp, c_fp, c_i, c_f, c_p, c_p, c_p]),
-    'rf_conv3d_split_pre_pm_supported': (c_i, [c_i, c_i, c_i, c_i]),
-    'rf_conv3d_split_pre_pm_k3_relu': (c_i, [c_p, c_i, c_i, c_i, c_p, c_i, c_fp, c_p, c_fp, c_p, c_p]),
-    'rf_conv3_up_split_packed_bytes': (c_sz, [c_i, c_i, c_i]),
-    'rf_conv3_up_split_pack_weight': (c_i, [c_fp, c_i, c_i, c_i, c_p, c_p]),
-    'rf_conv3d_up_split_supported': (c_i, [c_i, c_i, c_i, c_i, c_i]),
-    'rf_conv3d_up_split_stats_tiles': (c_i, [c_i, c_i, c_i, c_i, c_i]),
-    'rf_conv3d_up_split_k3_gn_relu': (c_i, [c_fp, c_i, c_fp, c_i, c_i, c_i, c_fp, c_p, c_i, c_fp, c_p, c_p]),
-    'rf_conv3d_k3_gn': (c_i, [c_fp, c_i, c_fp, c_i, c_i, c_i, c_fp, c_fp, c_i, c_i, c_fp, c_p]),
-    'rf_relu_backward': (c_i, [c_fp, c_fp, c_sz, c_fp, c_p]),
-    'rf_relu_backward_amax_slots': (c_i, []),
-    'rf_relu_backward_amax': (c_i, [c_fp, c_fp, c_sz, c_fp, c_fp, c_p]),
-    'rf_dgrad_scale_affine': (c_i, [c_fp, c_i, c_fp, c_fp, c_p]),
-    'rf_conv3d_split_k3_gn_supported': (c_i, [c_i, c_i, c_i, c_i]),
-    'rf_conv3d_split_k3_gn': (c_i, [c_fp, c_i, c_i, c_i, c_fp, c_p, c_i, c_i, c_fp, c_p]),
-    'rf_maxpool3d_2_backward': (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_fp, c_p]),
-    'rf_upsample3d_2': (c_i, [c_fp, c_i, c_i, c_i, c_fp, c_p]),
-    'rf_sumpool3d_2': (c_i, [c_fp, c_i, c_i, c_i, c_fp, c_p]),
-    'rf_gn_backward': (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_fp, c_i, c_f, c_fp, c_fp, c_fp, c_fp, c_p, c_sz, c_p]),
-    'rf_gn_backward_ws_bytes': (c_sz, [c_i, c_i, c_i]),
-    'rf_conv3d_k3_wgrad': (c_i, [c_fp, c_i, c_i, c_i, c_fp, c_fp, c_i, c_fp, c_p, c_sz, c_p]),
-    'rf_conv3d_k3_wgrad_ws_bytes': (c_sz, [c_i, c_i, c_i, c_i]),
-    'rf_conv3d_k3_wgrad_split_supported': (c_i, [c_i, c_i, c_i, c_i]),
-    'rf_conv3d_k3_wgrad_split_ws_bytes': (c_sz, [c_i, c_i, c_i, c_i]),
-    'rf_conv3d_k3_wgrad_split': (c_i, [c_fp, c_i, c_i, c_i, c_fp, c_fp, c_i, c_fp, c_fp, c_p, c_sz, c_p]),
-    'rf_conv3d_valid_leaky_backward_ws_bytes': (c_sz, [c_i, c_i, c_i]),
-    'rf_conv3d_valid_leaky_backward': (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_f, c_fp, c_fp, c_p, c_sz, c_p]),
-    'rf_convv_dgrad_packed_floats': (c_sz, [c_i, c_i, c_i]),
-    'rf_conv3d_valid_dgrad': (c_i, [c_fp, c_i, c_i, c_i, c_fp, c_i, c_i, c_i, c_i, c_fp, c_p]),
-    'rf_conv3d_valid_wgrad_ws_bytes': (c_sz, [c_i, c_i, c_i, c_i, c_i]),
-    'rf_conv3d_valid_wgrad': (c_i, [c_fp, c_i, c_i, c_i, c_fp, c_i, c_i, c_i, c_fp, c_p, c_sz, c_p]),
-    'rf_unfold3d': (c_i, [c_fp, c_i, c_i, c_i, c_i, c_fp, c_p]),
-    'rf_fold3d': (c_i, [c_fp, c_i, c_i, c_i, c_i, c_fp, c_p]),
-    'rf_linear_pack_weight': (c_i, [c_fp, c_i, c_i, c_fp, c_p]),
-    'rf_linear_packed_floats': (c_sz, [c_i, c_i]),
-    'rf_linear': (c_i, [c_fp, c_i, c_i, c_fp, c_fp, c_i, c_i, c_f, c_fp, c_p]),
-    'rf_linear_wgrad': (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_fp, c_p, c_sz, c_p]),
-    'rf_linear_wgrad_ws_bytes': (c_sz, [c_i, c_i, c_i]),
-    'rf_l2_normalize_rows': (c_i, [c_fp, c_i, c_i, c_f, c_p]),
-    'rf_attn_fuse': (c_i, [c_fp, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_f, c_fp, c_fp, c_fp, c_p]),
-    'rf_attn_gather_retrieved': (c_i, [c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_fp, c_p]),
-    'rf_attn_mlp_packed_floats': (c_sz, [c_i]),
-    'rf_attn_mlp_pack': (c_i, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_i, c_fp, c_p]),
-    'rf_attn_mlp_rows': (c_i, [c_fp, c_i, c_i, c_fp, c_fp, c_p]),
-    'rf_attn_mlp_split_packed_floats': (c_sz, [c_i]),
-    'rf_attn_mlp_split_pack': (c_i, [c_fp, c_fp, c_fp, c_fp, c_i, c_fp, c_p]),
-    'rf_attn_mlp_split_rows': (c_i, [c_fp, c_i, c_i, c_fp, c_fp, c_fp, c_p]),
-    'rf_attn_mlp_split_volume': (c_i, [c_fp, c_i, c_i, c_i, c_i, c_i, c_fp, c_fp, c_fp, c_p]),
-    'rf_attn_mlp_volume': (c_i, [c_fp, c_i, c_i, c_i, c_i, c_i, c_fp, c_fp, c_p]),
-    'rf_attn_weights': (c_i, [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_f, c_fp, c_fp, c_fp, c_p]),
-    'rf_attn_weights_sampled': (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_f, c_p, c_fp, c_fp, c_fp, c_fp, c_p]),
-    'rf_attn_blend': (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_fp, c_fp, c_fp, c_p]),
-    'rf_query_windows': (c_i, [c_fp, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_fp, c_p]),
-    'rf_gather_windows': (c_i, [c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_fp, c_p]),
-    'rf_gather_windows_split': (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p]),
-    'rf_db_pack_embeddings': (c_i, [c_fp, c_i64, c_i, c_fp, c_p]),
-    'rf_db_packed_floats': (c_sz, [c_i64, c_i]),
-    'rf_l2_topk': (c_i, [c_fp, c_i, c_i, c_fp, c_i64, c_i64, c_i, c_i, c_fp, c_p, c_p, c_sz, c_p]),
-    'rf_l2_topk_keys': (c_i, [c_fp, c_i, c_i, c_fp, c_i64, c_i64, c_i, c_i, c_p, c_p, c_sz, c_p]),
-    'rf_topk_merge_keys': (c_i, [c_p, c_i, c_i, c_i, c_fp, c_p, c_p]),
-    'rf_l2_topk_ws_bytes': (c_sz, [c_i, c_i64, c_i]),
-    'rf_topk_merge': (c_i, [c_fp, c_p, c_i, c_i, c_i, c_fp, c_p, c_p]),
-    'rf_demote_same_scene': (c_i, [c_fp, c_p, c_i, c_i, c_p, c_p, c_p, c_i, c_p, c_fp, c_p, c_p]),
-    'rf_gather_rows': (c_i, [c_fp, c_i64, c_p, c_i64, c_i, c_fp, c_p]),
-    'rf_conv3d_split_pre_pool_presplit_supported': (c_i, [c_i, c_i, c_i, c_i, c_i]),
-    'rf_conv3d_split_pre_k3_relu_pool_presplit': (c_i, [c_p, c_i, c_i, c_i, c_p, c_i, c_fp, c_p, c_fp, c_fp, c_i, c_f, c_p, c_p]),
-    'rf_conv3d_split_pre_pool_presplit_scratch_floats': (ctypes.c_size_t, [c_i]),
-    'rf_conv3d_split_pre_presplit_supported': (c_i, [c_i, c_i, c_i, c_i, c_i]),
-    'rf_conv3d_split_pre_presplit': (c_i, [c_p, c_i, c_i, c_i, c_p, c_i, c_fp, c_fp, c_i, c_f, c_p, c_p, c_p]),
-    'rf_conv3d_up_split_ch8_supported': (c_i, [c_i, c_i, c_i, c_i, c_i]),
-    'rf_conv3d_up_split_k3_gn_relu_ch8': (c_i, [c_fp, c_i, c_fp, c_i, c_i, c_i, c_fp, c_p, c_i, c_fp, c_p, c_p]),
-    'rf_conv3d_split_pointwise_ch8_supported': (c_i, [c_i, c_i, c_i, c_i]),
-    'rf_conv3d_split_k3_gn_relu_pointwise_tanh_ch8': (c_i, [c_fp, c_i, c_i, c_i, c_fp, c_p, c_i, c_fp, c_fp, c_f, c_f, c_fp, c_p]),
-    'rf_mc_classify': (c_i, [c_fp, c_i, c_i, c_i, c_f, c_p, c_p, c_p, c_p]),
-    'rf_mc_emit': (c_i, [c_fp, c_i, c_i, c_i, c_f, c_p, c_p, c_p, c_p, c_p, c_fp, c_p, c_p]),
-    'rf_gather_patches': (c_i, [c_fp, c_i64, c_p, c_i, c_i, c_f, c_f, c_f, c_f, c_i, c_fp, c_p]),
-    'rf_gather_patches_f16': (c_i, [c_p, c_i64, c_p, c_i, c_i, c_f, c_f, c_f, c_f, c_i, c_fp, c_p]),
-    'rf_compose_overlap': (c_i, [c_p, c_i, c_i64, c_fp, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_fp, c_fp, c_p]),
-    'rf_paste_chunks': (c_i, [c_fp, c_i, c_p, c_p, c_i, c_i64, c_i64, c_i, c_p, c_p]),
-    'rf_occupancy_stats_ws_bytes': (c_sz, [c_i, c_i, c_i, c_i, c_i]),
-    'rf_occupancy_stats': (c_i, [c_p, c_i, c_f, c_p, c_i, c_f, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_sz, c_p]),
-}
+
+def parse_header(text):
+    """name -> (restype, [argtypes], [parameter names]) for every function declaration of a header written in the vocabulary of
+    include/rfuse.h: block comments, preprocessor lines, the ``extern "C" {`` ... ``}`` bracket and declarations ``type name(type name, ...);``
+    that may span lines.  Anything else (a type outside _SCALARS, a parameter without a name, text that is no complete declaration)
+    raises: a wrong guess here is a wrong foreign call."""
+    text = re.sub(r'/\*.*?\*/', ' ', text, flags=re.S)
+    text = re.sub(r'^[ \t]*#.*$', ' ', text, flags=re.M)
+    text = re.sub(r'extern\s+"C"\s*\{|\}', ' ', text)
+
+    def where(chunk):
+        m = re.search(r'(\w+)\s*\(', chunk)
+        return '%s: %r' % (m.group(1) if m else '?', ' '.join(chunk.split()))
+
+    *decls, rest = text.split(';')
+    if rest.strip():
+        raise ValueError('declaration without its `;` -- %s' % where(rest))
+
+    def ctype(decl, fn, restype=False):
+        decl = ' '.join(decl.replace('*', ' * ').split())
+        if restype and decl == 'const char *':
+            return ctypes.c_char_p
+        if decl.endswith('*'):
+            return ctypes.c_void_p
+        if decl not in _SCALARS:
+            raise ValueError('%s: type %r is outside the vocabulary of the binding (%s, pointers)' % (fn, decl, ', '.join(_SCALARS)))
+        return _SCALARS[decl]
+
+    table = {}
+    for decl in decls:
+        m = re.fullmatch(r'\s*([\w\s*]+?)\b(\w+)\s*\(([\w\s*,]*)\)\s*', decl)
+        if m is None:
+            raise ValueError('cannot read the declaration of %s' % where(decl))
+        ret, fn, params = m.groups()
+        params = [] if params.strip() == 'void' else [re.fullmatch(r'\s*(\w[\w\s*]*[\s*])(\w+)\s*', q) for q in params.split(',')]
+        if None in params:
+            raise ValueError('%s: every parameter needs a type and a name' % fn)
+        table[fn] = (ctype(ret, fn, True), [ctype(q.group(1), fn) for q in params], [q.group(2) for q in params])
+    return table
+
+
+# name -> (restype, argtypes, parameter names): include/rfuse.h is the only description of the ABI
+SIGNATURES = parse_header(HEADER_PATH.read_text())
+
+
+def is_status(name):
+    """The header's rule: an ``int`` function whose last parameter is ``stream`` launches and returns 0 or an RF_E_* code; every other function returns a value."""
+    res, _, params = SIGNATURES[name]
+    return res is ctypes.c_int and params[-1:] == ['stream']
+
+
+def _raise_on_status(rc, fn, args):
+    if rc != 0:
+        check(rc, fn.__name__)
+    return rc
+
 
 _lib = None
 
 
 class _Library:
-    """The bound entry points as plain attributes (no indirection on the hot path).  ``start_profile`` swaps every stream-ordered
-    entry point for a wrapper that brackets the call with HIP events on the launch stream and records
+    """The bound entry points as plain attributes (no indirection on the hot path; the status check is the binding's own ``errcheck``).
+    ``start_profile`` swaps every ``int`` entry point that takes arguments for a wrapper that brackets the call with HIP events on the launch stream and records
     (name, integer arguments, start, end, positions of the null pointer arguments) -- bench.py's per-kernel table; ``stop_profile`` restores the direct bindings."""
 
     def __init__(self, cdll):
         self._cdll = cdll
         self._direct = {}
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args, _) in SIGNATURES.items():
             fn = getattr(cdll, name)      # AttributeError here == header/library mismatch
             fn.restype = res
             fn.argtypes = args
+            if is_status(name):
+                fn.errcheck = _raise_on_status      # a failed launch raises where it is made, under its own symbol
             self._direct[name] = fn
             setattr(self, name, fn)
 
@@ -197,10 +107,10 @@ class _Library:
                 records.append((name, tuple(a for a in args if isinstance(a, int)), e0, e1, tuple(i for i, a in enumerate(args) if a is None or (isinstance(a, ctypes.c_void_p) and not a.value))))
                 return rc
             return call
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args, _) in SIGNATURES.items():
             if only is not None and name not in only:
                 continue
-            if res is c_i and args and name not in ('rf_abi_version',):     # int-returning launches (all take the stream last)
+            if res is ctypes.c_int and args:     # the launches, and the *_supported / *_tiles queries made between them
                 setattr(self, name, timed(name, self._direct[name]))
 
     def stop_profile(self):
@@ -209,7 +119,7 @@ class _Library:
 
 
 def load():
-    """dlopen the library (once) and attach argument/return types.  Raises if it is not built."""
+    """dlopen the library (once) and attach argument/return types and the status check.  Raises if it is not built."""
     global _lib
     if _lib is not None:
         return _lib
@@ -222,6 +132,7 @@ def load():
 
 
 def check(rc, what):
+    """For callers that bind an entry point themselves; the bindings of ``load()`` check their own status."""
     if rc != 0:
         msg = load().rf_last_error()
         raise RuntimeError('%s failed (rc=%d): %s' % (what, rc, msg.decode() if msg else ''))

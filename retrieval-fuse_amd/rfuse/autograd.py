@@ -47,7 +47,7 @@ def _ws(dev, nbytes):
 @ops._device_scoped
 def relu_backward(dy, y):
     out = torch.empty_like(y)
-    _lib.check(_lib.load().rf_relu_backward(_p(dy), _p(y), y.numel(), _p(out), _stream()), 'rf_relu_backward')
+    _lib.load().rf_relu_backward(_p(dy), _p(y), y.numel(), _p(out), _stream())
     return out
 
 
@@ -57,7 +57,7 @@ def relu_backward_amax(dy, y):
     out = torch.empty_like(y)
     lib = _lib.load()
     amax = torch.empty(lib.rf_relu_backward_amax_slots(), dtype=torch.float32, device=y.device)       # per-workgroup maxima, reduced by the consumer
-    _lib.check(lib.rf_relu_backward_amax(_p(dy), _p(y), y.numel(), _p(out), _p(amax), _stream()), 'rf_relu_backward_amax')
+    lib.rf_relu_backward_amax(_p(dy), _p(y), y.numel(), _p(out), _p(amax), _stream())
     return out, amax
 
 
@@ -68,7 +68,7 @@ def dz_scale(amax, n, cout):
     affine with scale s for [n][cout] and the device pair (s, 1 / s)."""
     ident = torch.empty((n, cout, 4), dtype=torch.float32, device=amax.device)
     scales = torch.empty(2, dtype=torch.float32, device=amax.device)
-    _lib.check(_lib.load().rf_dgrad_scale_affine(_p(amax), n * cout, _p(ident), _p(scales), _stream()), 'rf_dgrad_scale_affine')
+    _lib.load().rf_dgrad_scale_affine(_p(amax), n * cout, _p(ident), _p(scales), _stream())
     return ident, scales
 
 
@@ -78,8 +78,7 @@ def dgrad_split(dz, ident, weight, cin):
     n, cout, edge = dz.shape[0], dz.shape[1], dz.shape[2]
     wt = weight.flip(2, 3, 4).transpose(0, 1).contiguous()          # [cin, cout, 3,3,3]: the data-gradient conv's weight
     out = torch.empty((n, cin, edge, edge, edge), dtype=torch.float32, device=dz.device)
-    _lib.check(_lib.load().rf_conv3d_split_k3_gn(_p(dz), cout, n, edge, _p(ident), _p(ops.pack_conv3_split_weight(wt)), cin, 0, _p(out), _stream()),
-               'rf_conv3d_split_k3_gn')
+    _lib.load().rf_conv3d_split_k3_gn(_p(dz), cout, n, edge, _p(ident), _p(ops.pack_conv3_split_weight(wt)), cin, 0, _p(out), _stream())
     return out
 
 
@@ -90,8 +89,7 @@ def conv3d_wgrad_split(x, aff, dz, scales, cout):
     lib = _lib.load()
     dw = torch.empty((cout, cin, 3, 3, 3), dtype=torch.float32, device=x.device)
     ws = _ws(x.device, lib.rf_conv3d_k3_wgrad_split_ws_bytes(cin, cout, n, edge))
-    _lib.check(lib.rf_conv3d_k3_wgrad_split(_p(x), cin, n, edge, _p(aff), _p(dz), cout, _p(scales), _p(dw), _p(ws), ws.numel(), _stream()),
-               'rf_conv3d_k3_wgrad_split')
+    lib.rf_conv3d_k3_wgrad_split(_p(x), cin, n, edge, _p(aff), _p(dz), cout, _p(scales), _p(dw), _p(ws), ws.numel(), _stream())
     return dw
 
 
@@ -105,7 +103,7 @@ def dgrad_split_supported(dz, weight, cin):
 def conv3d_gn(x, aff, w_packed, cout, relu):
     n, c, edge = x.shape[0], x.shape[1], x.shape[2]
     out = torch.empty((n, cout, edge, edge, edge), dtype=torch.float32, device=x.device)
-    _lib.check(_lib.load().rf_conv3d_k3_gn(_p(x), c, _p(None), 0, n, edge, _p(aff), _p(w_packed), cout, int(relu), _p(out), _stream()), 'rf_conv3d_k3_gn')
+    _lib.load().rf_conv3d_k3_gn(_p(x), c, _p(None), 0, n, edge, _p(aff), _p(w_packed), cout, int(relu), _p(out), _stream())
     return out
 
 
@@ -118,8 +116,7 @@ def gn_backward(x, dxn, gamma, groups, eps, inv_scale=None):
     dg = torch.empty(c, dtype=torch.float32, device=x.device)
     db = torch.empty(c, dtype=torch.float32, device=x.device)
     ws = _ws(x.device, lib.rf_gn_backward_ws_bytes(n, c, edge))
-    _lib.check(lib.rf_gn_backward(_p(x), _p(dxn), n, c, edge, _p(gamma), groups, eps, _p(inv_scale), _p(dx), _p(dg), _p(db), _p(ws), ws.numel(), _stream()),
-               'rf_gn_backward')
+    lib.rf_gn_backward(_p(x), _p(dxn), n, c, edge, _p(gamma), groups, eps, _p(inv_scale), _p(dx), _p(dg), _p(db), _p(ws), ws.numel(), _stream())
     return dx, dg, db
 
 
@@ -129,7 +126,7 @@ def conv3d_wgrad(x, aff, dz, cout):
     lib = _lib.load()
     dw = torch.empty((cout, cin, 3, 3, 3), dtype=torch.float32, device=x.device)
     ws = _ws(x.device, lib.rf_conv3d_k3_wgrad_ws_bytes(cin, cout, n, edge))
-    _lib.check(lib.rf_conv3d_k3_wgrad(_p(x), cin, n, edge, _p(aff), _p(dz), cout, _p(dw), _p(ws), ws.numel(), _stream()), 'rf_conv3d_k3_wgrad')
+    lib.rf_conv3d_k3_wgrad(_p(x), cin, n, edge, _p(aff), _p(dz), cout, _p(dw), _p(ws), ws.numel(), _stream())
     return dw
 
 
@@ -257,7 +254,7 @@ def upsample2(x):
     ops._req(x, 'x')
     n, c, e = x.shape[0], x.shape[1], x.shape[2]
     out = torch.empty((n, c, 2 * e, 2 * e, 2 * e), dtype=torch.float32, device=x.device)
-    _lib.check(_lib.load().rf_upsample3d_2(_p(x), n, c, e, _p(out), _stream()), 'rf_upsample3d_2')
+    _lib.load().rf_upsample3d_2(_p(x), n, c, e, _p(out), _stream())
     return out
 
 
@@ -266,7 +263,7 @@ def sumpool2(g):
     ops._req(g, 'g')
     n, c, e = g.shape[0], g.shape[1], g.shape[2]
     out = torch.empty((n, c, e // 2, e // 2, e // 2), dtype=torch.float32, device=g.device)
-    _lib.check(_lib.load().rf_sumpool3d_2(_p(g), n, c, e, _p(out), _stream()), 'rf_sumpool3d_2')
+    _lib.load().rf_sumpool3d_2(_p(g), n, c, e, _p(out), _stream())
     return out
 
 
@@ -275,7 +272,7 @@ def maxpool2_backward(x, g):
     ops._req(x, 'x'), ops._req(g, 'g')
     n, c, e = x.shape[0], x.shape[1], x.shape[2]
     dx = torch.empty_like(x)
-    _lib.check(_lib.load().rf_maxpool3d_2_backward(_p(x), _p(g), n, c, e, _p(dx), _stream()), 'rf_maxpool3d_2_backward')
+    _lib.load().rf_maxpool3d_2_backward(_p(x), _p(g), n, c, e, _p(dx), _stream())
     return dx
 
 

@@ -130,14 +130,14 @@ def marching_cubes(volume, level=0.75):
     table, count = _device_tables(v.device)
     ntri = torch.empty(X * Y * Z, dtype=torch.int32, device=v.device)
     flag = torch.empty(X * Y * Z * 3, dtype=torch.int32, device=v.device)
-    _lib.check(lib.rf_mc_classify(_p(v), X, Y, Z, float(level), _p(count), _p(ntri), _p(flag), _stream()), 'rf_mc_classify')
+    lib.rf_mc_classify(_p(v), X, Y, Z, float(level), _p(count), _p(ntri), _p(flag), _stream())
     tri_end, edge_end = torch.cumsum(ntri, 0, dtype=torch.int64), torch.cumsum(flag, 0, dtype=torch.int64)
     n_tri, n_vert = int(tri_end[-1].item()), int(edge_end[-1].item())            # the one host sync: output sizes
     tri_off, edge_off = (tri_end - ntri).contiguous(), (edge_end - flag).contiguous()
     verts = torch.empty((n_vert, 3), dtype=torch.float32, device=v.device)
     tris = torch.empty((n_tri, 3), dtype=torch.int32, device=v.device)
     if n_tri:
-        _lib.check(lib.rf_mc_emit(_p(v), X, Y, Z, float(level), _p(table), _p(tri_off), _p(edge_off), _p(ntri), _p(flag), _p(verts), _p(tris), _stream()), 'rf_mc_emit')
+        lib.rf_mc_emit(_p(v), X, Y, Z, float(level), _p(table), _p(tri_off), _p(edge_off), _p(ntri), _p(flag), _p(verts), _p(tris), _stream())
     return verts, tris
 
 

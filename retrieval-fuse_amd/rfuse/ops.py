@@ -87,7 +87,8 @@ class PackedWeight:
     """Caches the MFMA operand image of a Parameter; re-packs when the parameter is modified, moved or replaced."""
 
     def __init__(self, kind):
-        self.kind = kind        # 'conv3' | 'linear' | 'convv' | 'conv3up'
+        self.kind = kind        # a key of _PACKERS (end of this module)
+        self._pack = _PACKERS[kind]
         self._key = None
         self._packed = None
         self._ready = _PackedReady()
@@ -95,8 +96,7 @@ class PackedWeight:
     def get(self, w, *extra):
         key = (w.data_ptr(), w._version, tuple(w.shape), w.device) + extra
         if key != self._key:
-            self._packed = {'conv3': pack_conv3_weight, 'linear': pack_linear_weight, 'convv': pack_convv_weight,
-                            'convvl': pack_convv_lds_weight, 'convvv': pack_convv_valu_weight, 'conv3up': pack_conv3_up_weight, 'conv3ups': pack_conv3_up_split_weight, 'conv3s': pack_conv3_split_weight, 'conv3e2': pack_conv3_e2_split_weight, 'convvs': pack_convv_split_weight, 'convvpg': pack_convv_split_pg_weight, 'convvd': pack_convv_dgrad_weight}[self.kind](w, *extra)
+            self._packed = self._pack(w, *extra)
             self._key = key
             self._ready.packed_on(w.device)
         else:
@@ -133,15 +133,27 @@ class _PackedReady:
 
 # ------------------------------------------------------------------------------------------------ U-Net primitives
 
+def _pack_weight(stem, w, dims, dtype=torch.float32, not_taken=None):
+    """The operand image ``rf_<stem>_pack_weight(w, *dims)`` writes, in a fresh buffer of ``rf_<stem>_packed_floats(*dims)`` float32 values or, for
+    any other ``dtype``, ``rf_<stem>_packed_bytes(*dims)`` bytes.  ``not_taken``: the ValueError text where a size of 0 means that the form does
+    not take the layer."""
+    lib = _lib.load()
+    if dtype == torch.float32:
+        count = getattr(lib, 'rf_%s_packed_floats' % stem)(*dims)
+    else:
+        count = getattr(lib, 'rf_%s_packed_bytes' % stem)(*dims) // dtype.itemsize
+    if count == 0 and not_taken is not None:
+        raise ValueError(not_taken)
+    out = torch.empty(count, dtype=dtype, device=w.device)
+    getattr(lib, 'rf_%s_pack_weight' % stem)(_p(w.detach()), *dims, _p(out), _stream())
+    return out
+
+
 def pack_conv3_weight(w):
     _req(w.detach(), 'conv weight')
-    cout, cin = w.shape[0], w.shape[1]
     if tuple(w.shape[2:]) != (3, 3, 3):
         raise ValueError('pack_conv3_weight: expected an OIDHW 3x3x3 weight, got %s' % (tuple(w.shape),))
-    lib = _lib.load()
-    out = torch.empty(lib.rf_conv3_packed_floats(cout, cin), dtype=torch.float32, device=w.device)
-    _lib.check(lib.rf_conv3_pack_weight(_p(w.detach()), cout, cin, _p(out), _stream()), 'rf_conv3_pack_weight')
-    return out
+    return _pack_weight('conv3', w, (w.shape[0], w.shape[1]))
 
 
 def _src_dims(src0, src1):
@@ -170,16 +182,16 @@ def gn_affine(src0, src1, gamma, beta, groups, eps=1e-5):
     lib = _lib.load()
     aff = torch.empty((n, c, 4), dtype=torch.float32, device=dev)
     st0, st1 = _fresh_stats(src0), _fresh_stats(src1)
-    if USE_FUSED_STATS and (src0 is None or st0 is not None) and (src1 is None or st1 is not None):
+    if (src0 is None or st0 is not None) and (src1 is None or st1 is not None):
         # the producers (conv / max-pool epilogues) already emitted per-tile sums: no re-read of the activations
-        _lib.check(lib.rf_gn_from_stats(_p(st0[0]) if st0 else _p(None), c0, st0[1] if st0 else 0,
-                                        _p(st1[0]) if st1 else _p(None), c1, st1[1] if st1 else 0, n, edge,
-                                        _p(gamma.detach()), _p(beta.detach()), groups, eps, _p(aff), _stream()), 'rf_gn_from_stats')
+        lib.rf_gn_from_stats(_p(st0[0]) if st0 else _p(None), c0, st0[1] if st0 else 0,
+                             _p(st1[0]) if st1 else _p(None), c1, st1[1] if st1 else 0, n, edge,
+                             _p(gamma.detach()), _p(beta.detach()), groups, eps, _p(aff), _stream())
         return aff
     nbytes = lib.rf_gn_stats_ws_bytes(n, groups)
     ws = _workspace(dev, nbytes)
-    _lib.check(lib.rf_gn_stats(_p(src0), c0, _p(src1), c1, n, edge, _p(gamma.detach()), _p(beta.detach()), groups, eps,
-                               _p(aff), _p(ws), ws.numel(), _stream()), 'rf_gn_stats')
+    lib.rf_gn_stats(_p(src0), c0, _p(src1), c1, n, edge, _p(gamma.detach()), _p(beta.detach()), groups, eps,
+                    _p(aff), _p(ws), ws.numel(), _stream())
     return aff
 
 
@@ -190,7 +202,14 @@ def _check_affine(aff, n, c):
     return aff.device
 
 
-USE_FUSED_STATS = True          # producers attach (stats, tiles, version) to their outputs as ``tensor._rf_stats``
+def _attach_stats(t, tiles):
+    """The [n, c, tiles, 2] float64 buffer in which the kernel that writes ``t`` leaves per-tile (sum, sum of squares) of it, attached to ``t`` as
+    ``t._rf_stats = (stats, tiles, version)`` for the next layer's gn_affine; None for a tensor that is not written (``t`` None)."""
+    if t is None:
+        return None
+    stats = torch.empty((t.shape[0], t.shape[1], tiles, 2), dtype=torch.float64, device=t.device)
+    t._rf_stats = (stats, tiles, t._version)
+    return stats
 
 
 def _fresh_stats(t):
@@ -201,20 +220,13 @@ def _fresh_stats(t):
 
 def _conv_launch(lib, src0, c0, src1, c1, n, edge, aff, w_packed, cout, out):
     """MFMA conv launch; emits the output's GroupNorm statistics for the next layer when the tiling supports it."""
-    tiles = lib.rf_conv3d_stats_tiles(c0, c1, n, edge, cout) if USE_FUSED_STATS else 0
+    tiles = lib.rf_conv3d_stats_tiles(c0, c1, n, edge, cout)
     if tiles > 0:
-        stats = torch.empty((n, cout, tiles, 2), dtype=torch.float64, device=out.device)
-        _lib.check(lib.rf_conv3d_k3_gn_relu_stats(_p(src0), c0, _p(src1), c1, n, edge, _p(aff), _p(w_packed), cout, _p(out),
-                                                  _p(stats), _stream()), 'rf_conv3d_k3_gn_relu_stats')
-        out._rf_stats = (stats, tiles, out._version)
+        lib.rf_conv3d_k3_gn_relu_stats(_p(src0), c0, _p(src1), c1, n, edge, _p(aff), _p(w_packed), cout, _p(out),
+                                       _p(_attach_stats(out, tiles)), _stream())
     else:
-        _lib.check(lib.rf_conv3d_k3_gn_relu(_p(src0), c0, _p(src1), c1, n, edge, _p(aff), _p(w_packed), cout, _p(out),
-                                            _stream()), 'rf_conv3d_k3_gn_relu')
-
-
-# bench.py hook: time selected conv launches with HIP events recorded on the launch stream
-conv_event_filter = None        # callable(cin, cout, edge, n) -> bool
-conv_events = []                # [(start_event, end_event, flop issued, label)]; label = (entry point, arithmetic, (c0, c1, n, edge, cout))
+        lib.rf_conv3d_k3_gn_relu(_p(src0), c0, _p(src1), c1, n, edge, _p(aff), _p(w_packed), cout, _p(out),
+                                 _stream())
 
 
 def conv3d_gn_relu(src0, src1, aff, w_packed, cout, direct_weight=None):
@@ -223,16 +235,9 @@ def conv3d_gn_relu(src0, src1, aff, w_packed, cout, direct_weight=None):
     dev = _check_affine(aff, n, c0 + c1)
     out = torch.empty((n, cout, edge, edge, edge), dtype=torch.float32, device=dev)
     lib = _lib.load()
-    if conv_event_filter is not None and direct_weight is None and conv_event_filter(c0 + c1, cout, edge, n):
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-        _conv_launch(lib, src0, c0, src1, c1, n, edge, aff, w_packed, cout, out)
-        ev1.record()
-        conv_events.append((ev0, ev1, 2.0 * 27 * (c0 + c1) * cout * edge ** 3 * n, ('rf_conv3d_k3_gn_relu', 'fp32 MFMA', (c0, c1, n, edge, cout))))
-        return out
     if direct_weight is not None:
-        _lib.check(lib.rf_conv3d_k3_gn_relu_direct(_p(src0), c0, _p(src1), c1, n, edge, _p(aff), _p(direct_weight.detach()),
-                                                   cout, _p(out), _stream()), 'rf_conv3d_k3_gn_relu_direct')
+        lib.rf_conv3d_k3_gn_relu_direct(_p(src0), c0, _p(src1), c1, n, edge, _p(aff), _p(direct_weight.detach()),
+                                        cout, _p(out), _stream())
     else:
         _conv_launch(lib, src0, c0, src1, c1, n, edge, aff, w_packed, cout, out)
     return out
@@ -256,18 +261,10 @@ def conv3d_gn_relu_pool(src0, src1, aff, w_packed, cout, keep_full=True):
     lib = _lib.load()
     out = torch.empty((n, cout, edge, edge, edge), dtype=torch.float32, device=dev) if keep_full else None
     pooled = torch.empty((n, cout, edge // 2, edge // 2, edge // 2), dtype=torch.float32, device=dev)
-    stats = pstats = None
-    if USE_FUSED_STATS:
-        tiles = lib.rf_conv3d_stats_tiles(c0, c1, n, edge, cout)
-        pstats = torch.empty((n, cout, tiles, 2), dtype=torch.float64, device=dev)
-        if keep_full:
-            stats = torch.empty((n, cout, tiles, 2), dtype=torch.float64, device=dev)
-    _lib.check(lib.rf_conv3d_k3_gn_relu_pool(_p(src0), c0, _p(src1), c1, n, edge, _p(aff), _p(w_packed), cout, _p(out), _p(stats),
-                                             _p(pooled), _p(pstats), _stream()), 'rf_conv3d_k3_gn_relu_pool')
-    if stats is not None:
-        out._rf_stats = (stats, tiles, out._version)
-    if pstats is not None:
-        pooled._rf_stats = (pstats, tiles, pooled._version)
+    tiles = lib.rf_conv3d_stats_tiles(c0, c1, n, edge, cout)
+    pstats = _attach_stats(pooled, tiles)
+    lib.rf_conv3d_k3_gn_relu_pool(_p(src0), c0, _p(src1), c1, n, edge, _p(aff), _p(w_packed), cout, _p(out), _p(_attach_stats(out, tiles)),
+                                  _p(pooled), _p(pstats), _stream())
     return out, pooled
 
 
@@ -277,10 +274,7 @@ def pack_conv3_up_weight(w, c0):
     cout, cin = w.shape[0], w.shape[1]
     if tuple(w.shape[2:]) != (3, 3, 3) or not 0 <= c0 < cin:
         raise ValueError('pack_conv3_up_weight: expected an OIDHW 3x3x3 weight and 0 <= c0 < cin, got %s, c0=%d' % (tuple(w.shape), c0))
-    lib = _lib.load()
-    out = torch.empty(lib.rf_conv3_up_packed_floats(cout, c0, cin - c0), dtype=torch.float32, device=w.device)
-    _lib.check(lib.rf_conv3_up_pack_weight(_p(w.detach()), cout, c0, cin - c0, _p(out), _stream()), 'rf_conv3_up_pack_weight')
-    return out
+    return _pack_weight('conv3_up', w, (cout, c0, cin - c0))
 
 
 def conv_up_supported(src0, src1, cout):
@@ -299,21 +293,9 @@ def conv3d_up_gn_relu(src0, src1, aff, w_up_packed, cout):
     n, c0, c1, edge = _src_dims(src0, src1)
     out = torch.empty((n, cout, edge, edge, edge), dtype=torch.float32, device=_check_affine(aff, n, c0 + c1))
     lib = _lib.load()
-    stats = None
-    if USE_FUSED_STATS:
-        tiles = lib.rf_conv3d_up_stats_tiles(c0, c1, n, edge, cout)
-        stats = torch.empty((n, cout, tiles, 2), dtype=torch.float64, device=out.device)
-    timed = conv_event_filter is not None and conv_event_filter(c0 + c1, cout, edge, n)
-    if timed:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    _lib.check(lib.rf_conv3d_up_k3_gn_relu(_p(src0), c0, _p(src1), c1, n, edge, _p(aff), _p(w_up_packed), cout, _p(out),
-                                           _p(stats), _stream()), 'rf_conv3d_up_k3_gn_relu')
-    if timed:
-        ev1.record()
-        conv_events.append((ev0, ev1, conv_up_issued_flops(c0, c1, n, edge, cout), ('rf_conv3d_up_k3_gn_relu', 'fp32 MFMA', (c0, c1, n, edge, cout))))
-    if stats is not None:
-        out._rf_stats = (stats, tiles, out._version)
+    stats = _attach_stats(out, lib.rf_conv3d_up_stats_tiles(c0, c1, n, edge, cout))
+    lib.rf_conv3d_up_k3_gn_relu(_p(src0), c0, _p(src1), c1, n, edge, _p(aff), _p(w_up_packed), cout, _p(out),
+                                _p(stats), _stream())
     return out
 
 
@@ -375,13 +357,9 @@ def split_range_ok(weight, gamma=None, beta=None, group_elements=0):
 def pack_conv3_split_weight(w):
     """f16 fragment-order weight image of the split-operand box conv (csrc/conv3d_split.hip)."""
     _req(w.detach(), 'conv weight')
-    cout, cin = w.shape[0], w.shape[1]
     if tuple(w.shape[2:]) != (3, 3, 3):
         raise ValueError('pack_conv3_split_weight: expected an OIDHW 3x3x3 weight, got %s' % (tuple(w.shape),))
-    lib = _lib.load()
-    out = torch.empty(lib.rf_conv3_split_packed_bytes(cout, cin), dtype=torch.uint8, device=w.device)
-    _lib.check(lib.rf_conv3_split_pack_weight(_p(w.detach()), cout, cin, _p(out), _stream()), 'rf_conv3_split_pack_weight')
-    return out
+    return _pack_weight('conv3_split', w, (w.shape[0], w.shape[1]), torch.uint8)
 
 
 def conv_split_supported(src0, src1, cout):
@@ -404,36 +382,18 @@ def conv3d_split_gn_relu(src, aff, w_split_packed, cout, pool=None):
     out = torch.empty((n, cout, edge, edge, edge), dtype=torch.float32, device=dev) if pool != 'only' else None
     pooled = torch.empty((n, cout, edge // 2, edge // 2, edge // 2), dtype=torch.float32, device=dev) if pool is not None else None
     tiles = max(1, (edge // 8) ** 3)
-    stats = pstats = None
-    if USE_FUSED_STATS:
-        stats = torch.empty((n, cout, tiles, 2), dtype=torch.float64, device=dev) if out is not None else None
-        pstats = torch.empty((n, cout, tiles, 2), dtype=torch.float64, device=dev) if pooled is not None else None
-    timed = conv_event_filter is not None and conv_event_filter(cin, cout, edge, n)
-    if timed:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    _lib.check(lib.rf_conv3d_split_k3_gn_relu(_p(src), cin, n, edge, _p(aff), _p(w_split_packed), cout, _p(out), _p(stats), _p(pooled), _p(pstats),
-                                              _stream()), 'rf_conv3d_split_k3_gn_relu')
-    if timed:
-        ev1.record()
-        conv_events.append((ev0, ev1, conv_split_issued_flops(cin, n, edge, cout), ('rf_conv3d_split_k3_gn_relu', 'f16 split', (cin, 0, n, edge, cout))))
-    if stats is not None:
-        out._rf_stats = (stats, tiles, out._version)
-    if pstats is not None:
-        pooled._rf_stats = (pstats, tiles, pooled._version)
+    stats, pstats = _attach_stats(out, tiles), _attach_stats(pooled, tiles)
+    lib.rf_conv3d_split_k3_gn_relu(_p(src), cin, n, edge, _p(aff), _p(w_split_packed), cout, _p(out), _p(stats), _p(pooled), _p(pstats),
+                                   _stream())
     return out if pool is None else (out, pooled)
 
 
 def pack_conv3_e2_split_weight(w, edge=2):
     """f16 fragment-order image of the dense GEMM form of a 3x3x3 conv on whole 2^3 (edge 2) or 1^3 (edge 1) volumes (csrc/conv3d_e2_split.hip)."""
     _req(w.detach(), 'conv weight')
-    cout, cin = w.shape[0], w.shape[1]
     if tuple(w.shape[2:]) != (3, 3, 3) or edge not in (1, 2):
         raise ValueError('pack_conv3_e2_split_weight: expected an OIDHW 3x3x3 weight and edge 1 or 2, got %s, edge %r' % (tuple(w.shape), edge))
-    lib = _lib.load()
-    out = torch.empty(lib.rf_conv3_e2_split_packed_bytes(cout, cin, edge), dtype=torch.uint8, device=w.device)
-    _lib.check(lib.rf_conv3_e2_split_pack_weight(_p(w.detach()), cout, cin, edge, _p(out), _stream()), 'rf_conv3_e2_split_pack_weight')
-    return out
+    return _pack_weight('conv3_e2_split', w, (w.shape[0], w.shape[1], edge), torch.uint8)
 
 
 def conv_e2_split_supported(src, cout):
@@ -449,11 +409,7 @@ def conv3d_e2_split_gn_relu(src, aff, w_e2_packed, cout):
     n, cin, _, edge = _src_dims(src, None)
     dev = _check_affine(aff, n, cin)
     out = torch.empty((n, cout, edge, edge, edge), dtype=torch.float32, device=dev)
-    stats = torch.empty((n, cout, 1, 2), dtype=torch.float64, device=dev) if USE_FUSED_STATS else None
-    _lib.check(_lib.load().rf_conv3d_e2_split_k3_gn_relu(_p(src), cin, n, edge, _p(aff), _p(w_e2_packed), cout, _p(out), _p(stats), _stream()),
-               'rf_conv3d_e2_split_k3_gn_relu')
-    if stats is not None:
-        out._rf_stats = (stats, 1, out._version)
+    _lib.load().rf_conv3d_e2_split_k3_gn_relu(_p(src), cin, n, edge, _p(aff), _p(w_e2_packed), cout, _p(out), _p(_attach_stats(out, 1)), _stream())
     return out
 
 
@@ -476,8 +432,8 @@ def conv3d_cin1_presplit(x, in_gamma, in_beta, in_eps, w_packed, cout, next_gamm
     n, edge = x.shape[0], x.shape[2]
     lib = _lib.load()
     out = torch.empty(lib.rf_split_act_bytes(n, cout, edge), dtype=torch.uint8, device=x.device)
-    _lib.check(lib.rf_conv3d_cin1_presplit(_p(x), n, edge, _p(in_gamma.detach()), _p(in_beta.detach()), in_eps, _p(w_packed), cout, _p(next_gamma.detach()),
-                                           _p(next_beta.detach()), next_groups, eps, _p(out), _stream()), 'rf_conv3d_cin1_presplit')
+    lib.rf_conv3d_cin1_presplit(_p(x), n, edge, _p(in_gamma.detach()), _p(in_beta.detach()), in_eps, _p(w_packed), cout, _p(next_gamma.detach()),
+                                _p(next_beta.detach()), next_groups, eps, _p(out), _stream())
     return out
 
 
@@ -492,15 +448,8 @@ def conv3d_split_pointwise_tanh(x, gn_affine_t, w_split_packed, cout, pw_w, pw_b
     if pw_w.shape[0] != 1:
         raise NotImplementedError('conv3d_split_pointwise_tanh: one output channel (Conv3d(nf,1,1), model/refinement.py:54)')
     out = torch.empty((n, 1, edge, edge, edge), dtype=torch.float32, device=x.device)
-    timed = conv_event_filter is not None and conv_event_filter(cin, cout, edge, n)
-    if timed:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    _lib.check(_lib.load().rf_conv3d_split_k3_gn_relu_pointwise_tanh(_p(x), cin, n, edge, _p(gn_affine_t), _p(w_split_packed), cout, _p(pw_w.detach()), _p(pw_b.detach()),
-                                                                     post_add, post_mul, _p(out), _stream()), 'rf_conv3d_split_k3_gn_relu_pointwise_tanh')
-    if timed:
-        ev1.record()
-        conv_events.append((ev0, ev1, conv_split_issued_flops(cin, n, edge, cout), ('rf_conv3d_split_k3_gn_relu', 'f16 split', (cin, 0, n, edge, cout))))
+    _lib.load().rf_conv3d_split_k3_gn_relu_pointwise_tanh(_p(x), cin, n, edge, _p(gn_affine_t), _p(w_split_packed), cout, _p(pw_w.detach()), _p(pw_b.detach()),
+                                                          post_add, post_mul, _p(out), _stream())
     return out
 
 
@@ -516,8 +465,8 @@ def conv3d_split_presplit(x, gn_affine_t, w_split_packed, cout, next_gamma, next
     n, cin, edge = x.shape[0], x.shape[1], x.shape[2]
     lib = _lib.load()
     out = torch.empty(lib.rf_split_act_bytes(n, cout, edge), dtype=torch.uint8, device=x.device)
-    _lib.check(lib.rf_conv3d_split_presplit(_p(x), cin, n, edge, _p(gn_affine_t), _p(w_split_packed), cout, _p(next_gamma.detach()), _p(next_beta.detach()),
-                                            next_groups, eps, _p(out), _p(None), _stream()), 'rf_conv3d_split_presplit')
+    lib.rf_conv3d_split_presplit(_p(x), cin, n, edge, _p(gn_affine_t), _p(w_split_packed), cout, _p(next_gamma.detach()), _p(next_beta.detach()),
+                                 next_groups, eps, _p(out), _p(None), _stream())
     return out
 
 
@@ -532,7 +481,7 @@ def conv_up_split_presplit_supported(x, upsampled, cout, next_groups):
 def conv_up_split_presplit_pm_supported(x, upsampled, cout, next_groups, next_cout):
     """the decoder pair can hand over in PARITY-MAJOR slot order: the persistent producer (rf_conv3d_up_split_presplit_pm) AND the persistent consumer
     (rf_conv3d_split_pre_pm_k3_relu) take the shapes"""
-    if not USE_PRESPLIT or not USE_PRESPLIT_PM or CONV_ARITH != 'split' or upsampled is None or x is None:
+    if not USE_PRESPLIT or CONV_ARITH != 'split' or upsampled is None or x is None:
         return False
     lib = _lib.load()
     n, edge = upsampled.shape[0], 2 * upsampled.shape[2]
@@ -550,20 +499,12 @@ def conv3d_up_split_presplit(x, upsampled, gn_affine_t, w_packed, cout, next_gam
     lib = _lib.load()
     out = torch.empty(lib.rf_split_act_bytes(n, cout, edge), dtype=torch.uint8, device=upsampled.device)
     c1 = upsampled.shape[1]
-    timed = conv_event_filter is not None and conv_event_filter(c0 + c1, cout, edge, n)
-    if timed:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    entry = 'rf_conv3d_up_split_presplit_pm' if parity_major else 'rf_conv3d_up_split_presplit'
-    _lib.check(getattr(lib, entry)(_p(x), c0, _p(upsampled), c1, n, edge, _p(gn_affine_t), _p(w_packed), cout, _p(next_gamma.detach()),
-                                   _p(next_beta.detach()), next_groups, eps, _p(out), _p(None), _stream()), entry)
-    if timed:
-        ev1.record()
-        conv_events.append((ev0, ev1, conv_up_split_issued_flops(c0, c1, n, edge, cout), ('rf_conv3d_up_split_presplit', 'f16 split', (c0, c1, n, edge, cout))))
+    launch = lib.rf_conv3d_up_split_presplit_pm if parity_major else lib.rf_conv3d_up_split_presplit
+    launch(_p(x), c0, _p(upsampled), c1, n, edge, _p(gn_affine_t), _p(w_packed), cout, _p(next_gamma.detach()),
+           _p(next_beta.detach()), next_groups, eps, _p(out), _p(None), _stream())
     return out
 
 
-USE_PRESPLIT_PM = True          # False: the decoder pair hands over in the linear slot order (cross-checks)
 USE_PREPOOL = True              # False: the level-0 max-pool hands an fp32 tensor to the next level (the round-3 route; kept for cross-checks)
 
 
@@ -598,8 +539,8 @@ def conv3d_split_pre_relu_pool_presplit(pre, cin, n, edge, w_split_packed, cout,
     half = edge // 2
     scratch = torch.empty(lib.rf_conv3d_split_pre_pool_presplit_scratch_floats(cout), dtype=torch.float32, device=dev)
     out = torch.empty(lib.rf_split_act_bytes(n, cout, half), dtype=torch.uint8, device=dev)
-    _lib.check(lib.rf_conv3d_split_pre_k3_relu_pool_presplit(_p(pre), cin, n, edge, _p(w_split_packed), cout, _p(scratch), _p(None), _p(next_gamma.detach()),
-                                                             _p(next_beta.detach()), next_groups, eps, _p(out), _stream()), 'rf_conv3d_split_pre_k3_relu_pool_presplit')
+    lib.rf_conv3d_split_pre_k3_relu_pool_presplit(_p(pre), cin, n, edge, _p(w_split_packed), cout, _p(scratch), _p(None), _p(next_gamma.detach()),
+                                                  _p(next_beta.detach()), next_groups, eps, _p(out), _stream())
     return None, PreSplit(out, n, cout, half)
 
 
@@ -611,8 +552,8 @@ def conv3d_split_pre_presplit(pre, w_split_packed, cout, next_gamma, next_beta, 
     """relu(conv(.)) of a PreSplit input (whole 8^3 samples), emitted as the PreSplit input of the NEXT layer"""
     lib = _lib.load()
     out = torch.empty(lib.rf_split_act_bytes(pre.n, cout, pre.edge), dtype=torch.uint8, device=pre.device)
-    _lib.check(lib.rf_conv3d_split_pre_presplit(_p(pre.data), pre.channels, pre.n, pre.edge, _p(w_split_packed), cout, _p(next_gamma.detach()), _p(next_beta.detach()),
-                                                next_groups, eps, _p(out), _p(None), _stream()), 'rf_conv3d_split_pre_presplit')
+    lib.rf_conv3d_split_pre_presplit(_p(pre.data), pre.channels, pre.n, pre.edge, _p(w_split_packed), cout, _p(next_gamma.detach()), _p(next_beta.detach()),
+                                     next_groups, eps, _p(out), _p(None), _stream())
     return PreSplit(out, pre.n, cout, pre.edge)
 
 
@@ -624,23 +565,9 @@ def conv3d_split_pre_relu(pre, cin, n, edge, w_split_packed, cout, pool=None, pa
     out = torch.empty((n, cout, edge, edge, edge), dtype=torch.float32, device=dev) if pool != 'only' else None
     pooled = torch.empty((n, cout, edge // 2, edge // 2, edge // 2), dtype=torch.float32, device=dev) if pool is not None else None
     tiles = 1 if parity_major else lib.rf_conv3d_split_pre_stats_tiles(cin, n, edge, cout)      # one per 8^3 box, or one per sample (persistent form)
-    stats = pstats = None
-    if USE_FUSED_STATS:
-        stats = torch.empty((n, cout, tiles, 2), dtype=torch.float64, device=dev) if out is not None else None
-        pstats = torch.empty((n, cout, tiles, 2), dtype=torch.float64, device=dev) if pooled is not None else None
-    timed = conv_event_filter is not None and conv_event_filter(cin, cout, edge, n)
-    if timed:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    entry = 'rf_conv3d_split_pre_pm_k3_relu' if parity_major else 'rf_conv3d_split_pre_k3_relu'
-    _lib.check(getattr(lib, entry)(_p(pre), cin, n, edge, _p(w_split_packed), cout, _p(out), _p(stats), _p(pooled), _p(pstats), _stream()), entry)
-    if timed:
-        ev1.record()
-        conv_events.append((ev0, ev1, conv_split_issued_flops(cin, n, edge, cout), ('rf_conv3d_split_pre_k3_relu', 'f16 split', (cin, 0, n, edge, cout))))
-    if stats is not None:
-        out._rf_stats = (stats, tiles, out._version)
-    if pstats is not None:
-        pooled._rf_stats = (pstats, tiles, pooled._version)
+    stats, pstats = _attach_stats(out, tiles), _attach_stats(pooled, tiles)
+    launch = lib.rf_conv3d_split_pre_pm_k3_relu if parity_major else lib.rf_conv3d_split_pre_k3_relu
+    launch(_p(pre), cin, n, edge, _p(w_split_packed), cout, _p(out), _p(stats), _p(pooled), _p(pstats), _stream())
     if pool is None:
         return out
     return out, pooled
@@ -658,10 +585,7 @@ def pack_conv3_up_split_weight(w, c0):
     cout, cin = w.shape[0], w.shape[1]
     if tuple(w.shape[2:]) != (3, 3, 3) or not 0 <= c0 < cin:
         raise ValueError('pack_conv3_up_split_weight: expected an OIDHW 3x3x3 weight and 0 <= c0 < cin, got %s, c0=%d' % (tuple(w.shape), c0))
-    lib = _lib.load()
-    out = torch.empty(lib.rf_conv3_up_split_packed_bytes(cout, c0, cin - c0), dtype=torch.uint8, device=w.device)
-    _lib.check(lib.rf_conv3_up_split_pack_weight(_p(w.detach()), cout, c0, cin - c0, _p(out), _stream()), 'rf_conv3_up_split_pack_weight')
-    return out
+    return _pack_weight('conv3_up_split', w, (cout, c0, cin - c0), torch.uint8)
 
 
 def conv_up_split_supported(src0, src1, cout):
@@ -677,19 +601,9 @@ def conv3d_up_split_gn_relu(src0, src1, aff, w_split_packed, cout):
     n, c0, c1, edge = _src_dims(src0, src1)
     out = torch.empty((n, cout, edge, edge, edge), dtype=torch.float32, device=_check_affine(aff, n, c0 + c1))
     lib = _lib.load()
-    tiles = lib.rf_conv3d_up_split_stats_tiles(c0, c1, n, edge, cout)
-    stats = torch.empty((n, cout, tiles, 2), dtype=torch.float64, device=out.device) if USE_FUSED_STATS else None
-    timed = conv_event_filter is not None and conv_event_filter(c0 + c1, cout, edge, n)
-    if timed:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    _lib.check(lib.rf_conv3d_up_split_k3_gn_relu(_p(src0), c0, _p(src1), c1, n, edge, _p(aff), _p(w_split_packed), cout, _p(out),
-                                                 _p(stats), _stream()), 'rf_conv3d_up_split_k3_gn_relu')
-    if timed:
-        ev1.record()
-        conv_events.append((ev0, ev1, conv_up_split_issued_flops(c0, c1, n, edge, cout), ('rf_conv3d_up_split_k3_gn_relu', 'f16 split', (c0, c1, n, edge, cout))))
-    if stats is not None:
-        out._rf_stats = (stats, tiles, out._version)
+    stats = _attach_stats(out, lib.rf_conv3d_up_split_stats_tiles(c0, c1, n, edge, cout))
+    lib.rf_conv3d_up_split_k3_gn_relu(_p(src0), c0, _p(src1), c1, n, edge, _p(aff), _p(w_split_packed), cout, _p(out),
+                                      _p(stats), _stream())
     return out
 
 
@@ -699,7 +613,7 @@ USE_CH8 = True                  # False: the final decoder's conv pair hands ove
 def conv_up_split_ch8_supported(src1, cout, next_cout):
     """True when the final decoder's pair can hand over channel-interleaved: the box form of the decoder-form split conv writes ch8
     (rf_conv3d_up_split_k3_gn_relu_ch8) and the persistent z-column form of the second conv + pointwise head reads it."""
-    if not USE_CH8 or not USE_FUSED_STATS or not USE_CONV_UP or CONV_ARITH != 'split' or src1 is None:
+    if not USE_CH8 or not USE_CONV_UP or CONV_ARITH != 'split' or src1 is None:
         return False
     n, c1, edge = src1.shape[0], src1.shape[1], 2 * src1.shape[2]
     lib = _lib.load()
@@ -715,8 +629,7 @@ def conv3d_up_split_gn_relu_ch8(src1, aff, w_split_packed, cout):
     out = torch.empty((n, cout // 8, edge, edge, edge, 8), dtype=torch.float32, device=dev)
     tiles = lib.rf_conv3d_up_split_stats_tiles(0, c1, n, edge, cout)
     stats = torch.empty((n, cout, tiles, 2), dtype=torch.float64, device=dev)
-    _lib.check(lib.rf_conv3d_up_split_k3_gn_relu_ch8(_p(None), 0, _p(src1), c1, n, edge, _p(aff), _p(w_split_packed), cout, _p(out), _p(stats), _stream()),
-               'rf_conv3d_up_split_k3_gn_relu_ch8')
+    lib.rf_conv3d_up_split_k3_gn_relu_ch8(_p(None), 0, _p(src1), c1, n, edge, _p(aff), _p(w_split_packed), cout, _p(out), _p(stats), _stream())
     return out, stats, tiles
 
 
@@ -725,7 +638,7 @@ def gn_affine_from_stats(stats, tiles, n, c, edge, gamma, beta, groups, eps=1e-5
     if c < groups:
         groups = 1
     aff = torch.empty((n, c, 4), dtype=torch.float32, device=stats.device)
-    _lib.check(_lib.load().rf_gn_from_stats(_p(stats), c, tiles, _p(None), 0, 0, n, edge, _p(gamma.detach()), _p(beta.detach()), groups, eps, _p(aff), _stream()), 'rf_gn_from_stats')
+    _lib.load().rf_gn_from_stats(_p(stats), c, tiles, _p(None), 0, 0, n, edge, _p(gamma.detach()), _p(beta.detach()), groups, eps, _p(aff), _stream())
     return aff
 
 
@@ -735,8 +648,8 @@ def conv3d_split_pointwise_tanh_ch8(x_ch8, gn_affine_t, w_split_packed, cout, pw
     n, cin, edge = x_ch8.shape[0], x_ch8.shape[1] * 8, x_ch8.shape[2]
     _check_affine(gn_affine_t, n, cin)
     out = torch.empty((n, 1, edge, edge, edge), dtype=torch.float32, device=x_ch8.device)
-    _lib.check(_lib.load().rf_conv3d_split_k3_gn_relu_pointwise_tanh_ch8(_p(x_ch8), cin, n, edge, _p(gn_affine_t), _p(w_split_packed), cout, _p(pw_w.detach()), _p(pw_b.detach()),
-                                                                         post_add, post_mul, _p(out), _stream()), 'rf_conv3d_split_k3_gn_relu_pointwise_tanh_ch8')
+    _lib.load().rf_conv3d_split_k3_gn_relu_pointwise_tanh_ch8(_p(x_ch8), cin, n, edge, _p(gn_affine_t), _p(w_split_packed), cout, _p(pw_w.detach()), _p(pw_b.detach()),
+                                                              post_add, post_mul, _p(out), _stream())
     return out
 
 
@@ -770,13 +683,7 @@ def maxpool2(x):
     n, c, edge = x.shape[0], x.shape[1], x.shape[2]
     out = torch.empty((n, c, edge // 2, edge // 2, edge // 2), dtype=torch.float32, device=x.device)
     lib = _lib.load()
-    if USE_FUSED_STATS:
-        tiles = lib.rf_maxpool_stats_tiles(edge)
-        stats = torch.empty((n, c, tiles, 2), dtype=torch.float64, device=x.device)
-        _lib.check(lib.rf_maxpool3d_2_stats(_p(x), n, c, edge, _p(out), _p(stats), _stream()), 'rf_maxpool3d_2_stats')
-        out._rf_stats = (stats, tiles, out._version)
-    else:
-        _lib.check(lib.rf_maxpool3d_2(_p(x), n, c, edge, _p(out), _stream()), 'rf_maxpool3d_2')
+    lib.rf_maxpool3d_2_stats(_p(x), n, c, edge, _p(out), _p(_attach_stats(out, lib.rf_maxpool_stats_tiles(edge))), _stream())
     return out
 
 
@@ -787,18 +694,13 @@ def conv1x1_tanh(x, w, b, post_add=0.0, post_mul=1.0):
     n, c = x.shape[0], x.shape[1]
     vox = x[0, 0].numel()
     out = torch.empty((n, 1) + tuple(x.shape[2:]), dtype=torch.float32, device=x.device)
-    _lib.check(_lib.load().rf_conv1x1_tanh(_p(x), n, c, vox, _p(w.detach()), _p(b.detach()), post_add, post_mul, _p(out), _stream()),
-               'rf_conv1x1_tanh')
+    _lib.load().rf_conv1x1_tanh(_p(x), n, c, vox, _p(w.detach()), _p(b.detach()), post_add, post_mul, _p(out), _stream())
     return out
 
 
 def pack_convv_weight(w):
     _req(w.detach(), 'conv weight')
-    cout, cin, k = w.shape[0], w.shape[1], w.shape[2]
-    lib = _lib.load()
-    out = torch.empty(lib.rf_convv_packed_floats(cout, cin, k), dtype=torch.float32, device=w.device)
-    _lib.check(lib.rf_convv_pack_weight(_p(w.detach()), cout, cin, k, _p(out), _stream()), 'rf_convv_pack_weight')
-    return out
+    return _pack_weight('convv', w, tuple(w.shape[:3]))
 
 
 def conv3d_valid_leaky_mfma(x, w_packed, bias, cout, k, stride, slope):
@@ -807,26 +709,19 @@ def conv3d_valid_leaky_mfma(x, w_packed, bias, cout, k, stride, slope):
     n, cin, s = x.shape[0], x.shape[1], x.shape[2]
     so = (s - k) // stride + 1
     out = torch.empty((n, cout, so, so, so), dtype=torch.float32, device=x.device)
-    _lib.check(_lib.load().rf_conv3d_valid_leaky_mfma(_p(x), n, cin, s, _p(w_packed), _p(bias.detach() if bias is not None else None), cout, k,
-                                                      stride, slope, _p(out), _stream()), 'rf_conv3d_valid_leaky_mfma')
+    _lib.load().rf_conv3d_valid_leaky_mfma(_p(x), n, cin, s, _p(w_packed), _p(bias.detach() if bias is not None else None), cout, k,
+                                           stride, slope, _p(out), _stream())
     return out
 
 
 def pack_convv_lds_weight(w):
     _req(w.detach(), 'conv weight')
-    cout, cin, k = w.shape[0], w.shape[1], w.shape[2]
-    lib = _lib.load()
-    out = torch.empty(lib.rf_convv_lds_packed_floats(cout, cin, k), dtype=torch.float32, device=w.device)
-    _lib.check(lib.rf_convv_lds_pack_weight(_p(w.detach()), cout, cin, k, _p(out), _stream()), 'rf_convv_lds_pack_weight')
-    return out
-
-
-USE_CONVV_LDS = True            # False: every valid-conv layer runs the gather form
+    return _pack_weight('convv_lds', w, tuple(w.shape[:3]))
 
 
 def conv_valid_lds_supported(x, cout, k, stride):
     """True when the LDS-staged form (rf_conv3d_valid_leaky_lds) takes this layer (output edge >= 8 and a tile that fits LDS)."""
-    return USE_CONVV_LDS and bool(_lib.load().rf_conv3d_valid_lds_supported(x.shape[0], x.shape[1], x.shape[2], cout, k, stride))
+    return bool(_lib.load().rf_conv3d_valid_lds_supported(x.shape[0], x.shape[1], x.shape[2], cout, k, stride))
 
 
 def conv3d_valid_leaky_lds(x, w_packed, bias, cout, k, stride, slope):
@@ -835,22 +730,16 @@ def conv3d_valid_leaky_lds(x, w_packed, bias, cout, k, stride, slope):
     n, cin, s = x.shape[0], x.shape[1], x.shape[2]
     so = (s - k) // stride + 1
     out = torch.empty((n, cout, so, so, so), dtype=torch.float32, device=x.device)
-    _lib.check(_lib.load().rf_conv3d_valid_leaky_lds(_p(x), n, cin, s, _p(w_packed), _p(bias.detach() if bias is not None else None), cout, k,
-                                                     stride, slope, _p(out), _stream()), 'rf_conv3d_valid_leaky_lds')
+    _lib.load().rf_conv3d_valid_leaky_lds(_p(x), n, cin, s, _p(w_packed), _p(bias.detach() if bias is not None else None), cout, k,
+                                          stride, slope, _p(out), _stream())
     return out
 
 
 def pack_convv_split_weight(w, s, stride):
     """f16 fragment image of the split-operand valid conv for input edge s (the tile / chunk plan depends on the layer's input size)"""
     _req(w.detach(), 'conv weight')
-    cout, cin, k = w.shape[0], w.shape[1], w.shape[2]
-    lib = _lib.load()
-    nbytes = lib.rf_convv_split_packed_bytes(cout, cin, k, s, stride)
-    if nbytes == 0:
-        raise ValueError('pack_convv_split_weight: layer %s @%d^3 stride %d is not taken by the split form' % (tuple(w.shape), s, stride))
-    out = torch.empty(nbytes // 2, dtype=torch.float16, device=w.device)
-    _lib.check(lib.rf_convv_split_pack_weight(_p(w.detach()), cout, cin, k, s, stride, _p(out), _stream()), 'rf_convv_split_pack_weight')
-    return out
+    return _pack_weight('convv_split', w, tuple(w.shape[:3]) + (s, stride), torch.float16,
+                        'pack_convv_split_weight: layer %s @%d^3 stride %d is not taken by the split form' % (tuple(w.shape), s, stride))
 
 
 def conv_valid_split_supported(x, cout, k, stride):
@@ -880,8 +769,8 @@ def conv3d_valid_leaky_split(x, w_packed, bias, cout, k, stride, slope, out_spli
     n, cin, s = xt.shape[0], xt.shape[1], xt.shape[2]
     so = (s - k) // stride + 1
     out = torch.empty((n, cout, so, so, so), dtype=torch.float32, device=xt.device)
-    _lib.check(_lib.load().rf_conv3d_valid_leaky_split_ex(_p(xt), int(in_split), n, cin, s, _p(w_packed), _p(bias.detach() if bias is not None else None), cout, k,
-                                                          stride, slope, _p(out), int(out_split), _stream()), 'rf_conv3d_valid_leaky_split')
+    _lib.load().rf_conv3d_valid_leaky_split_ex(_p(xt), int(in_split), n, cin, s, _p(w_packed), _p(bias.detach() if bias is not None else None), cout, k,
+                                               stride, slope, _p(out), int(out_split), _stream())
     return SplitActs(out) if out_split else out
 
 
@@ -896,14 +785,8 @@ def conv_valid_split_pg_supported(shape, cout, k, stride):
 def pack_convv_split_pg_weight(w, s, stride):
     """weight image (tables + f16 fragments) of the persistent grid form for input edge s"""
     _req(w.detach(), 'conv weight')
-    cout, cin, k = w.shape[0], w.shape[1], w.shape[2]
-    lib = _lib.load()
-    nbytes = lib.rf_convv_split_pg_packed_bytes(cout, cin, k, s, stride)
-    if nbytes == 0:
-        raise ValueError('pack_convv_split_pg_weight: layer %s @%d^3 stride %d is not taken by the persistent grid form' % (tuple(w.shape), s, stride))
-    out = torch.empty(nbytes // 2, dtype=torch.float16, device=w.device)
-    _lib.check(lib.rf_convv_split_pg_pack_weight(_p(w.detach()), cout, cin, k, s, stride, _p(out), _stream()), 'rf_convv_split_pg_pack_weight')
-    return out
+    return _pack_weight('convv_split_pg', w, tuple(w.shape[:3]) + (s, stride), torch.float16,
+                        'pack_convv_split_pg_weight: layer %s @%d^3 stride %d is not taken by the persistent grid form' % (tuple(w.shape), s, stride))
 
 
 def conv3d_valid_leaky_split_pg(x, w_packed, bias, cout, k, stride, slope):
@@ -916,8 +799,8 @@ def conv3d_valid_leaky_split_pg(x, w_packed, bias, cout, k, stride, slope):
     n, cin, s = xt.shape[0], xt.shape[1], xt.shape[2]
     so = (s - k) // stride + 1
     out = torch.empty((n, cout, so, so, so), dtype=torch.float32, device=xt.device)
-    _lib.check(_lib.load().rf_conv3d_valid_leaky_split_pg(_p(xt), n, cin, s, _p(w_packed), _p(bias.detach() if bias is not None else None), cout, k, stride, slope,
-                                                          _p(out), _stream()), 'rf_conv3d_valid_leaky_split_pg')
+    _lib.load().rf_conv3d_valid_leaky_split_pg(_p(xt), n, cin, s, _p(w_packed), _p(bias.detach() if bias is not None else None), cout, k, stride, slope,
+                                               _p(out), _stream())
     return SplitActs(out)
 
 
@@ -943,8 +826,8 @@ def conv3d_valid_leaky_valu(x, w_t, bias, stride, slope, out_split=False):
     cout, k = w_t.shape[4], w_t.shape[1]
     so = (s - k) // stride + 1
     out = torch.empty((n, cout, so, so, so), dtype=torch.float32, device=x.device)
-    _lib.check(_lib.load().rf_conv3d_valid_leaky_valu_ex(_p(x), n, cin, s, _p(w_t), _p(bias.detach() if bias is not None else None), cout, k,
-                                                         stride, slope, _p(out), int(out_split), _stream()), 'rf_conv3d_valid_leaky_valu')
+    _lib.load().rf_conv3d_valid_leaky_valu_ex(_p(x), n, cin, s, _p(w_t), _p(bias.detach() if bias is not None else None), cout, k,
+                                              stride, slope, _p(out), int(out_split), _stream())
     return SplitActs(out) if out_split else out
 
 
@@ -954,14 +837,13 @@ def conv3d_valid_leaky(x, w, bias, stride, slope):
     cout, k = w.shape[0], w.shape[2]
     so = (s - k) // stride + 1
     out = torch.empty((n, cout, so, so, so), dtype=torch.float32, device=x.device)
-    _lib.check(_lib.load().rf_conv3d_valid_leaky(_p(x), n, cin, s, _p(w.detach()), _p(bias.detach() if bias is not None else None), cout, k,
-                                                 stride, slope, _p(out), _stream()), 'rf_conv3d_valid_leaky')
+    _lib.load().rf_conv3d_valid_leaky(_p(x), n, cin, s, _p(w.detach()), _p(bias.detach() if bias is not None else None), cout, k,
+                                      stride, slope, _p(out), _stream())
     return out
 
 
 # ------------------------------------------------------------------------------------- valid conv backward (patch encoders)
 
-@_device_scoped
 def conv3d_valid_leaky_backward(dy, y, slope):
     """dz = y > 0 ? dy : slope * dy from the saved output y, and db = sum of dz over samples and voxels (float64 across workgroups) -> (dz, db)"""
     _req(dy, 'dy'), _req(y, 'y')
@@ -972,8 +854,7 @@ def conv3d_valid_leaky_backward(dy, y, slope):
     dz = torch.empty_like(y)
     db = torch.empty(cout, dtype=torch.float32, device=y.device)
     ws = _workspace(y.device, lib.rf_conv3d_valid_leaky_backward_ws_bytes(n, cout, so))
-    _lib.check(lib.rf_conv3d_valid_leaky_backward(_p(dy), _p(y), n, cout, so, slope, _p(dz), _p(db), _p(ws), ws.numel(), _stream()),
-               'rf_conv3d_valid_leaky_backward')
+    lib.rf_conv3d_valid_leaky_backward(_p(dy), _p(y), n, cout, so, slope, _p(dz), _p(db), _p(ws), ws.numel(), _stream())
     return dz, db
 
 
@@ -987,18 +868,16 @@ def pack_convv_dgrad_weight(w):
     return out
 
 
-@_device_scoped
 def conv3d_valid_dgrad(dz, wd_packed, cin, k, stride, s):
     """data gradient of the valid strided conv: dz [n, cout, so^3] -> dx [n, cin, s^3] (wd_packed from pack_convv_dgrad_weight); planes of x that no
     output reads get 0"""
     _req(dz, 'dz'), _req(wd_packed, 'wd_packed')
     n, cout, so = dz.shape[0], dz.shape[1], dz.shape[2]
     dx = torch.empty((n, cin, s, s, s), dtype=torch.float32, device=dz.device)
-    _lib.check(_lib.load().rf_conv3d_valid_dgrad(_p(dz), n, cout, so, _p(wd_packed), cin, k, stride, s, _p(dx), _stream()), 'rf_conv3d_valid_dgrad')
+    _lib.load().rf_conv3d_valid_dgrad(_p(dz), n, cout, so, _p(wd_packed), cin, k, stride, s, _p(dx), _stream())
     return dx
 
 
-@_device_scoped
 def conv3d_valid_wgrad(x, dz, k, stride):
     """weight gradient of the valid strided conv: x [n, cin, s^3], dz [n, cout, so^3] -> dW [cout, cin, k, k, k] (split K, float64 slice sum)"""
     _req(x, 'x'), _req(dz, 'dz')
@@ -1009,7 +888,7 @@ def conv3d_valid_wgrad(x, dz, k, stride):
     lib = _lib.load()
     dw = torch.empty((cout, cin, k, k, k), dtype=torch.float32, device=x.device)
     ws = _workspace(x.device, lib.rf_conv3d_valid_wgrad_ws_bytes(n, cin, cout, so, k))
-    _lib.check(lib.rf_conv3d_valid_wgrad(_p(x), n, cin, s, _p(dz), cout, k, stride, _p(dw), _p(ws), ws.numel(), _stream()), 'rf_conv3d_valid_wgrad')
+    lib.rf_conv3d_valid_wgrad(_p(x), n, cin, s, _p(dz), cout, k, stride, _p(dw), _p(ws), ws.numel(), _stream())
     return dw
 
 
@@ -1020,7 +899,7 @@ def unfold3d(x, e):
     b, c, s = x.shape[0], x.shape[1], x.shape[2]
     r = s // e
     rows = torch.empty((b * r * r * r, c, e, e, e), dtype=torch.float32, device=x.device)
-    _lib.check(_lib.load().rf_unfold3d(_p(x), b, c, s, e, _p(rows), _stream()), 'rf_unfold3d')
+    _lib.load().rf_unfold3d(_p(x), b, c, s, e, _p(rows), _stream())
     return rows
 
 
@@ -1032,7 +911,7 @@ def fold3d(rows, r, e, c):
     if b * c * s * s * s != total:
         raise ValueError('fold3d: %d values do not tile [b,%d,%d^3]' % (total, c, s))
     x = torch.empty((b, c, s, s, s), dtype=torch.float32, device=rows.device)
-    _lib.check(_lib.load().rf_fold3d(_p(rows), b, c, s, e, _p(x), _stream()), 'rf_fold3d')
+    _lib.load().rf_fold3d(_p(rows), b, c, s, e, _p(x), _stream())
     return x
 
 
@@ -1041,18 +920,15 @@ def fold3d(rows, r, e, c):
 def pack_linear_weight(w):
     _req(w.detach(), 'linear weight')
     nout, nin = w.shape
-    lib = _lib.load()
-    out = torch.empty(lib.rf_linear_packed_floats(nout, nin), dtype=torch.float32, device=w.device)
-    _lib.check(lib.rf_linear_pack_weight(_p(w.detach()), nout, nin, _p(out), _stream()), 'rf_linear_pack_weight')
-    return out
+    return _pack_weight('linear', w, (nout, nin))
 
 
 def linear(x, w_packed, bias, nout, act=ACT_NONE, slope=0.0):
     _req(x, 'x')
     rows, nin = x.shape
     y = torch.empty((rows, nout), dtype=torch.float32, device=x.device)
-    _lib.check(_lib.load().rf_linear(_p(x), rows, nin, _p(w_packed), _p(bias.detach() if bias is not None else None), nout, act, slope,
-                                     _p(y), _stream()), 'rf_linear')
+    _lib.load().rf_linear(_p(x), rows, nin, _p(w_packed), _p(bias.detach() if bias is not None else None), nout, act, slope,
+                          _p(y), _stream())
     return y
 
 
@@ -1066,13 +942,13 @@ def linear_wgrad(a, b):
     nbytes = lib.rf_linear_wgrad_ws_bytes(k, m, n)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=a.device)
     dw = torch.empty((m, n), dtype=torch.float32, device=a.device)
-    _lib.check(lib.rf_linear_wgrad(_p(a), _p(b), k, m, n, _p(dw), _p(ws), nbytes, _stream()), 'rf_linear_wgrad')
+    lib.rf_linear_wgrad(_p(a), _p(b), k, m, n, _p(dw), _p(ws), nbytes, _stream())
     return dw
 
 
 def l2_normalize_rows_(x, eps=1e-12):
     _req(x, 'x')
-    _lib.check(_lib.load().rf_l2_normalize_rows(_p(x), x.shape[0], x.shape[1], eps, _stream()), 'rf_l2_normalize_rows')
+    _lib.load().rf_l2_normalize_rows(_p(x), x.shape[0], x.shape[1], eps, _stream())
     return x
 
 
@@ -1082,7 +958,7 @@ def attn_gather_retrieved(src, layout, b, k, c, s, e, t=0):
     _req(src, 'src')
     r = s // e
     p = torch.empty((b * r * r * r, k, c, e, e, e), dtype=torch.float32, device=src.device)
-    _lib.check(_lib.load().rf_attn_gather_retrieved(_p(src), layout, b, k, c, s, e, t, _p(p), _stream()), 'rf_attn_gather_retrieved')
+    _lib.load().rf_attn_gather_retrieved(_p(src), layout, b, k, c, s, e, t, _p(p), _stream())
     return p
 
 
@@ -1098,8 +974,8 @@ def attn_fuse(x, p, xf, pf, noise, mode, sharpness, debug=False):
     out = torch.empty_like(x)
     sc = torch.empty((b, k), dtype=torch.float32, device=x.device) if debug else None
     wt = torch.empty((b, k), dtype=torch.float32, device=x.device) if debug else None
-    _lib.check(_lib.load().rf_attn_fuse(_p(x), _p(p), _p(xf), _p(pf), _p(noise), b, k, d, f, mode, sharpness, _p(out), _p(sc), _p(wt),
-                                        _stream()), 'rf_attn_fuse')
+    _lib.load().rf_attn_fuse(_p(x), _p(p), _p(xf), _p(pf), _p(noise), b, k, d, f, mode, sharpness, _p(out), _p(sc), _p(wt),
+                             _stream())
     return (out, sc, wt) if debug else out
 
 
@@ -1140,9 +1016,9 @@ def pack_attn_mlp(params):
                          'got %s' % (shapes,))
     lib = _lib.load()
     out = torch.empty(lib.rf_attn_mlp_packed_floats(n_in), dtype=torch.float32, device=params[0].device)
-    _lib.check(lib.rf_attn_mlp_pack(*[_p(t.detach()) for t in params], n_in, _p(out), _stream()), 'rf_attn_mlp_pack')
+    lib.rf_attn_mlp_pack(*[_p(t.detach()) for t in params], n_in, _p(out), _stream())
     split = torch.empty(lib.rf_attn_mlp_split_packed_floats(n_in), dtype=torch.float32, device=params[0].device)
-    _lib.check(lib.rf_attn_mlp_split_pack(*[_p(t.detach()) for t in params[0::2]], n_in, _p(split), _stream()), 'rf_attn_mlp_split_pack')
+    lib.rf_attn_mlp_split_pack(*[_p(t.detach()) for t in params[0::2]], n_in, _p(split), _stream())
     return out, split
 
 
@@ -1153,9 +1029,9 @@ def attn_mlp_rows(x, packed):
     out = torch.empty((rows, 32), dtype=torch.float32, device=x.device)
     img, split = packed
     if CONV_ARITH == 'split' and split is not None:
-        _lib.check(_lib.load().rf_attn_mlp_split_rows(_p(x), rows, n_in, _p(img), _p(split), _p(out), _stream()), 'rf_attn_mlp_split_rows')
+        _lib.load().rf_attn_mlp_split_rows(_p(x), rows, n_in, _p(img), _p(split), _p(out), _stream())
     else:
-        _lib.check(_lib.load().rf_attn_mlp_rows(_p(x), rows, n_in, _p(img), _p(out), _stream()), 'rf_attn_mlp_rows')
+        _lib.load().rf_attn_mlp_rows(_p(x), rows, n_in, _p(img), _p(out), _stream())
     return out
 
 
@@ -1169,9 +1045,9 @@ def attn_mlp_volume(src, b, kv, c, s, t, packed):
     out = torch.empty((b * r * r * r * kv, 32), dtype=torch.float32, device=src.device)
     img, split = packed
     if CONV_ARITH == 'split' and split is not None:
-        _lib.check(_lib.load().rf_attn_mlp_split_volume(_p(src), b, kv, c, s, t, _p(img), _p(split), _p(out), _stream()), 'rf_attn_mlp_split_volume')
+        _lib.load().rf_attn_mlp_split_volume(_p(src), b, kv, c, s, t, _p(img), _p(split), _p(out), _stream())
     else:
-        _lib.check(_lib.load().rf_attn_mlp_volume(_p(src), b, kv, c, s, t, _p(img), _p(out), _stream()), 'rf_attn_mlp_volume')
+        _lib.load().rf_attn_mlp_volume(_p(src), b, kv, c, s, t, _p(img), _p(out), _stream())
     return out
 
 
@@ -1186,8 +1062,7 @@ def attn_weights(xf, pf, noise, k, mode, sharpness, debug=False):
     w = torch.empty((rows, k), dtype=torch.float32, device=xf.device)
     sw = torch.empty((rows,), dtype=torch.float32, device=xf.device)
     sc = torch.empty((rows, k), dtype=torch.float32, device=xf.device) if debug else None
-    _lib.check(_lib.load().rf_attn_weights(_p(xf), _p(pf), _p(noise), rows, k, f, mode, sharpness, _p(w), _p(sw), _p(sc), _stream()),
-               'rf_attn_weights')
+    _lib.load().rf_attn_weights(_p(xf), _p(pf), _p(noise), rows, k, f, mode, sharpness, _p(w), _p(sw), _p(sc), _stream())
     return (w, sw, sc) if debug else (w, sw)
 
 
@@ -1207,8 +1082,7 @@ def attn_weights_sampled(xf, pf, k, sharpness, rng_state, want_noise=False):
     w = torch.empty((rows, k), dtype=torch.float32, device=xf.device)
     sw = torch.empty((rows,), dtype=torch.float32, device=xf.device)
     nz = torch.empty((rows, k), dtype=torch.float32, device=xf.device) if want_noise else None
-    _lib.check(_lib.load().rf_attn_weights_sampled(_p(xf), _p(pf), rows, k, f, sharpness, _p(rng_state), _p(w), _p(sw), _p(None), _p(nz), _stream()),
-               'rf_attn_weights_sampled')
+    _lib.load().rf_attn_weights_sampled(_p(xf), _p(pf), rows, k, f, sharpness, _p(rng_state), _p(w), _p(sw), _p(None), _p(nz), _stream())
     return (w, sw, nz) if want_noise else (w, sw)
 
 
@@ -1219,7 +1093,7 @@ def attn_blend(x, retrieved, k, t, weights, switches):
     if retrieved.numel() != b * k * c * s * s * s:
         raise ValueError('attn_blend: retrieved features do not match %d x %d volumes' % (b, k))
     out = torch.empty_like(x)
-    _lib.check(_lib.load().rf_attn_blend(_p(x), _p(retrieved), b, k, c, s, t, _p(weights), _p(switches), _p(out), _stream()), 'rf_attn_blend')
+    _lib.load().rf_attn_blend(_p(x), _p(retrieved), b, k, c, s, t, _p(weights), _p(switches), _p(out), _stream())
     return out
 
 
@@ -1230,7 +1104,7 @@ def query_windows(raw, ps, ctx, pad_value, mean, std):
     b, s = raw.shape[0], raw.shape[-1]
     npatch, w = s // ps, ps + 2 * ctx
     out = torch.empty((b * npatch ** 3, 1, w, w, w), dtype=torch.float32, device=raw.device)
-    _lib.check(_lib.load().rf_query_windows(_p(raw), b, s, ps, ctx, pad_value, mean, std, _p(out), _stream()), 'rf_query_windows')
+    _lib.load().rf_query_windows(_p(raw), b, s, ps, ctx, pad_value, mean, std, _p(out), _stream())
     return out
 
 
@@ -1243,9 +1117,9 @@ def gather_windows(grid, w, step, npatch):
     n, c, g = gt.shape[0], gt.shape[1], gt.shape[2]
     out = torch.empty((n * npatch ** 3, c, w, w, w), dtype=torch.float32, device=gt.device)
     if split:
-        _lib.check(_lib.load().rf_gather_windows_split(_p(gt), n, c, g, w, step, npatch, _p(out), _stream()), 'rf_gather_windows_split')
+        _lib.load().rf_gather_windows_split(_p(gt), n, c, g, w, step, npatch, _p(out), _stream())
         return SplitActs(out)
-    _lib.check(_lib.load().rf_gather_windows(_p(gt), n, c, g, w, step, npatch, _p(out), _stream()), 'rf_gather_windows')
+    _lib.load().rf_gather_windows(_p(gt), n, c, g, w, step, npatch, _p(out), _stream())
     return out
 
 
@@ -1269,7 +1143,7 @@ def db_pack_embeddings(emb):
     n, dim = emb.shape
     lib = _lib.load()
     out = torch.empty(lib.rf_db_packed_floats(n, dim), dtype=torch.float32, device=emb.device)
-    _lib.check(lib.rf_db_pack_embeddings(_p(emb), n, dim, _p(out), _stream()), 'rf_db_pack_embeddings')
+    lib.rf_db_pack_embeddings(_p(emb), n, dim, _p(out), _stream())
     return out
 
 
@@ -1285,7 +1159,7 @@ def l2_topk(q, db_packed, n, row_base, k2, algo=TOPK_AUTO):
     idx = torch.empty((nq, k2), dtype=torch.int64, device=q.device)
     nbytes = lib.rf_l2_topk_ws_bytes(nq, n, k2)
     ws = _workspace(q.device, nbytes)
-    _lib.check(lib.rf_l2_topk(_p(q), nq, dim, _p(db_packed), n, row_base, k2, algo, _p(dist), _p(idx), _p(ws), ws.numel(), _stream()), 'rf_l2_topk')
+    lib.rf_l2_topk(_p(q), nq, dim, _p(db_packed), n, row_base, k2, algo, _p(dist), _p(idx), _p(ws), ws.numel(), _stream())
     return dist, idx
 
 
@@ -1297,7 +1171,7 @@ def l2_topk_keys(q, db_packed, n, row_base, k2, algo=TOPK_AUTO):
     keys = torch.empty((nq, k2), dtype=torch.int64, device=q.device)
     nbytes = lib.rf_l2_topk_ws_bytes(nq, n, k2)
     ws = _workspace(q.device, nbytes)
-    _lib.check(lib.rf_l2_topk_keys(_p(q), nq, dim, _p(db_packed), n, row_base, k2, algo, _p(keys), _p(ws), ws.numel(), _stream()), 'rf_l2_topk_keys')
+    lib.rf_l2_topk_keys(_p(q), nq, dim, _p(db_packed), n, row_base, k2, algo, _p(keys), _p(ws), ws.numel(), _stream())
     return keys
 
 
@@ -1307,7 +1181,7 @@ def topk_merge_keys(key_parts):
     parts, nq, k2 = key_parts.shape
     dist = torch.empty((nq, k2), dtype=torch.float32, device=key_parts.device)
     idx = torch.empty((nq, k2), dtype=torch.int64, device=key_parts.device)
-    _lib.check(_lib.load().rf_topk_merge_keys(_p(key_parts), parts, nq, k2, _p(dist), _p(idx), _stream()), 'rf_topk_merge_keys')
+    _lib.load().rf_topk_merge_keys(_p(key_parts), parts, nq, k2, _p(dist), _p(idx), _stream())
     return dist, idx
 
 
@@ -1317,7 +1191,7 @@ def topk_merge(dist_parts, idx_parts):
     parts, nq, k2 = dist_parts.shape
     dist = torch.empty((nq, k2), dtype=torch.float32, device=dist_parts.device)
     idx = torch.empty((nq, k2), dtype=torch.int64, device=dist_parts.device)
-    _lib.check(_lib.load().rf_topk_merge(_p(dist_parts), _p(idx_parts), parts, nq, k2, _p(dist), _p(idx), _stream()), 'rf_topk_merge')
+    _lib.load().rf_topk_merge(_p(dist_parts), _p(idx_parts), parts, nq, k2, _p(dist), _p(idx), _stream())
     return dist, idx
 
 
@@ -1337,8 +1211,8 @@ def demote_same_scene(dist, idx, db_meta, query_scene, K, query_keep=None):
     out_meta = torch.empty((nq, K, 7), dtype=torch.int32, device=dev)
     out_dist = torch.empty((nq, K), dtype=torch.float32, device=dev)
     out_idx = torch.empty((nq, K), dtype=torch.int64, device=dev)
-    _lib.check(_lib.load().rf_demote_same_scene(_p(dist), _p(idx), nq, k2, _p(db_meta), _p(query_scene), _p(query_keep), K, _p(out_meta),
-                                                _p(out_dist), _p(out_idx), _stream()), 'rf_demote_same_scene')
+    _lib.load().rf_demote_same_scene(_p(dist), _p(idx), nq, k2, _p(db_meta), _p(query_scene), _p(query_keep), K, _p(out_meta),
+                                     _p(out_dist), _p(out_idx), _stream())
     return out_meta, out_dist, out_idx
 
 
@@ -1347,7 +1221,7 @@ def gather_rows(src, idx):
     _req(src, 'src'), _req(idx, 'idx', torch.int64)
     width = src[0].numel()
     out = torch.empty((idx.numel(),) + tuple(src.shape[1:]), dtype=torch.float32, device=src.device)
-    _lib.check(_lib.load().rf_gather_rows(_p(src), src.shape[0], _p(idx), idx.numel(), width, _p(out), _stream()), 'rf_gather_rows')
+    _lib.load().rf_gather_rows(_p(src), src.shape[0], _p(idx), idx.numel(), width, _p(out), _stream())
     return out
 
 
@@ -1366,8 +1240,8 @@ def gather_patches(db_volumes, meta, chunks, K, trunc_fill, trunc_ratio, mean, s
     else:
         out = torch.empty((chunks, K, 64, 64, 64), dtype=torch.float32, device=dev)
     lib = _lib.load()
-    fn, name = (lib.rf_gather_patches_f16, 'rf_gather_patches_f16') if half else (lib.rf_gather_patches, 'rf_gather_patches')
-    _lib.check(fn(_p(db_volumes), db_volumes.shape[0], _p(meta), chunks, K, trunc_fill, trunc_ratio, mean, std, layout, _p(out), _stream()), name)
+    launch = lib.rf_gather_patches_f16 if half else lib.rf_gather_patches
+    launch(_p(db_volumes), db_volumes.shape[0], _p(meta), chunks, K, trunc_fill, trunc_ratio, mean, std, layout, _p(out), _stream())
     return out
 
 
@@ -1384,8 +1258,8 @@ def compose_overlap(db_volumes, mapping, boxes, K, size, trunc_fill, trunc_ratio
     sx, sy, sz = (int(v) for v in size)
     out = torch.empty((K, sx, sy, sz), dtype=torch.float32, device=db_volumes.device)
     ws = torch.empty((K, sx, sy, sz), dtype=torch.float32, device=db_volumes.device)
-    _lib.check(_lib.load().rf_compose_overlap(_p(db_volumes), int(half), db_volumes.shape[0], _p(mapping), _p(boxes), P, K, sx, sy, sz, trunc_fill, trunc_ratio,
-                                              _p(out), _p(ws), _stream()), 'rf_compose_overlap')
+    _lib.load().rf_compose_overlap(_p(db_volumes), int(half), db_volumes.shape[0], _p(mapping), _p(boxes), P, K, sx, sy, sz, trunc_fill, trunc_ratio,
+                                   _p(out), _p(ws), _stream())
     return out
 
 
@@ -1395,12 +1269,16 @@ def paste_chunks(df, sel, dst, sx, sy, flat, round_half=True):
     _req(df, 'df'), _req(sel, 'sel', torch.int32), _req(dst, 'dst', torch.int64), _req(flat, 'flat', torch.float64)
     if tuple(df.shape[1:]) != (1, 64, 64, 64) or sel.numel() != dst.numel():
         raise ValueError('paste_chunks: df must be [b, 1, 64, 64, 64] and sel / dst of one length (got %s, %d, %d)' % (tuple(df.shape), sel.numel(), dst.numel()))
-    _lib.check(_lib.load().rf_paste_chunks(_p(df), df.shape[0], _p(sel), _p(dst), sel.numel(), int(sx), int(sy), 1 if round_half else 0, _p(flat), _stream()),
-               'rf_paste_chunks')
+    _lib.load().rf_paste_chunks(_p(df), df.shape[0], _p(sel), _p(dst), sel.numel(), int(sx), int(sy), 1 if round_half else 0, _p(flat), _stream())
 
 
-# every public tensor op is scoped to its tensors' device (see _device_scoped)
+# every public function of this module is scoped to its tensors' device here, once (see _device_scoped); no function carries the decorator itself
 for _name, _fn in list(vars(sys.modules[__name__]).items()):
     if isinstance(_fn, type(_device_scoped)) and _fn.__module__ == __name__ and not _name.startswith('_'):
         setattr(sys.modules[__name__], _name, _device_scoped(_fn))
 del _name, _fn
+
+# PackedWeight kinds -> the (device-scoped) function that packs them; extra arguments of PackedWeight.get() go to it
+_PACKERS = {'conv3': pack_conv3_weight, 'conv3up': pack_conv3_up_weight, 'conv3ups': pack_conv3_up_split_weight, 'conv3s': pack_conv3_split_weight,
+            'conv3e2': pack_conv3_e2_split_weight, 'convv': pack_convv_weight, 'convvl': pack_convv_lds_weight, 'convvv': pack_convv_valu_weight,
+            'convvs': pack_convv_split_weight, 'convvpg': pack_convv_split_pg_weight, 'convvd': pack_convv_dgrad_weight, 'linear': pack_linear_weight}
