@@ -19,6 +19,7 @@
 #include "common.h"
 #include "attn_row.h"
 #include "split_operand.h"
+#include "philox.h"
 
 // The scalar arithmetic here restates torch expressions op by op (every product and sum rounded).  This file is built
 // with -ffp-contract=off (csrc/build.py): hipcc's default -ffp-contract=fast fuses a*b+c in the backend, where neither
@@ -481,16 +482,6 @@ static int am_volume(const float* src, int b, int kv, int c, int s, int t, const
 // exponential_ from the global generator): Philox4x32-10 keyed by a 64-bit seed, counter = (row, draw index, offset), four draws per call;
 // u = (24 random bits + 0.5) / 2^24 in (0, 1), g = -log(-log(u)).  The stream is this library's own (torch's generator cannot be advanced from
 // inside a kernel); what the reference fixes is the DISTRIBUTION, which tests/test_kernels_gpu.py checks against torch's sampler.
-__device__ __forceinline__ void rf_philox4x32_10(unsigned (&c)[4], unsigned k0, unsigned k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned long long p0 = 0xD2511F53ull * c[0], p1 = 0xCD9E8D57ull * c[2];
-        const unsigned n0 = (unsigned)(p1 >> 32) ^ c[1] ^ k0, n2 = (unsigned)(p0 >> 32) ^ c[3] ^ k1;
-        c[1] = (unsigned)p1; c[3] = (unsigned)p0; c[0] = n0; c[2] = n2;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-}
-
 __device__ __forceinline__ void rf_gumbel_row(unsigned long long seed, unsigned long long offset, int row, int K, float (&g)[RF_MAX_K]) {
 #pragma unroll
     for (int q = 0; q < RF_MAX_K / 4; ++q) {

@@ -1,9 +1,12 @@
-"""ctypes binding of librfuse_hip.so (the C ABI declared in include/rfuse.h).
+"""ctypes binding of librfuse_hip.so (the C ABI declared in include/rfuse.h, and the evaluation ABI of include/rfuse_eval.h).
 
 The argument and return types are read from the header itself at import (``parse_header``): there is no second copy of the ABI to keep
 in step.  There is NO fallback: if the library is missing a RuntimeError is raised, and every entry point that returns a status
 (``is_status``) raises a RuntimeError with ``rf_last_error()`` when that status is not 0.  ``import torch`` must come
 first so that the HIP runtime the library binds to is the one PyTorch-ROCm already loaded (same SONAME).
+
+``load()`` binds include/rfuse.h (``SIGNATURES``; the profiling wrapper brackets these); ``load_eval()`` binds include/rfuse_eval.h
+(``EVAL_SIGNATURES``: the mesh metrics, rfuse/mesh_metrics.py) from the same shared object, under the same status rule.
 """
 import ctypes
 import os
@@ -15,6 +18,7 @@ import torch  # noqa: F401  (loads libamdhip64 before we dlopen)
 _HERE = Path(__file__).resolve().parent
 LIB_PATH = Path(os.environ.get('RFUSE_LIB', _HERE / 'librfuse_hip.so'))
 HEADER_PATH = _HERE.parents[1] / 'include' / 'rfuse.h'
+EVAL_HEADER_PATH = _HERE.parents[1] / 'include' / 'rfuse_eval.h'
 
 # every scalar type include/rfuse.h uses; any pointer is a c_void_p, and `const char*` as a return type a c_char_p
 _SCALARS = {'int': ctypes.c_int, 'float': ctypes.c_float, 'size_t': ctypes.c_size_t, 'int64_t': ctypes.c_int64, 'long long': ctypes.c_int64}
@@ -62,11 +66,12 @@ def parse_header(text):
 
 # name -> (restype, argtypes, parameter names): include/rfuse.h is the only description of the ABI
 SIGNATURES = parse_header(HEADER_PATH.read_text())
+EVAL_SIGNATURES = parse_header(EVAL_HEADER_PATH.read_text())
 
 
-def is_status(name):
+def is_status(name, table=None):
     """The header's rule: an ``int`` function whose last parameter is ``stream`` launches and returns 0 or an RF_E_* code; every other function returns a value."""
-    res, _, params = SIGNATURES[name]
+    res, _, params = (SIGNATURES if table is None else table)[name]
     return res is ctypes.c_int and params[-1:] == ['stream']
 
 
@@ -77,6 +82,7 @@ def _raise_on_status(rc, fn, args):
 
 
 _lib = None
+_eval = None
 
 
 class _Library:
@@ -84,14 +90,15 @@ class _Library:
     ``start_profile`` swaps every ``int`` entry point that takes arguments for a wrapper that brackets the call with HIP events on the launch stream and records
     (name, integer arguments, start, end, positions of the null pointer arguments) -- bench.py's per-kernel table; ``stop_profile`` restores the direct bindings."""
 
-    def __init__(self, cdll):
+    def __init__(self, cdll, table=SIGNATURES):
         self._cdll = cdll
+        self._table = table
         self._direct = {}
-        for name, (res, args, _) in SIGNATURES.items():
+        for name, (res, args, _) in table.items():
             fn = getattr(cdll, name)      # AttributeError here == header/library mismatch
             fn.restype = res
             fn.argtypes = args
-            if is_status(name):
+            if is_status(name, table):
                 fn.errcheck = _raise_on_status      # a failed launch raises where it is made, under its own symbol
             self._direct[name] = fn
             setattr(self, name, fn)
@@ -107,7 +114,7 @@ class _Library:
                 records.append((name, tuple(a for a in args if isinstance(a, int)), e0, e1, tuple(i for i, a in enumerate(args) if a is None or (isinstance(a, ctypes.c_void_p) and not a.value))))
                 return rc
             return call
-        for name, (res, args, _) in SIGNATURES.items():
+        for name, (res, args, _) in self._table.items():
             if only is not None and name not in only:
                 continue
             if res is ctypes.c_int and args:     # the launches, and the *_supported / *_tiles queries made between them
@@ -129,6 +136,14 @@ def load():
             '(or __graft_entry__.build()).  There is no CPU fallback for the refinement hot path.' % LIB_PATH)
     _lib = _Library(ctypes.CDLL(str(LIB_PATH)))
     return _lib
+
+
+def load_eval():
+    """The entry points of include/rfuse_eval.h, bound from the library ``load()`` opened (one dlopen, one rf_last_error)."""
+    global _eval
+    if _eval is None:
+        _eval = _Library(load()._cdll, EVAL_SIGNATURES)
+    return _eval
 
 
 def check(rc, what):

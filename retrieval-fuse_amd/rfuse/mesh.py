@@ -154,6 +154,36 @@ def export_obj(vertices, triangles, path):
             f.write('\n')
 
 
+def load_obj(path):
+    """Wavefront .obj -> (vertices float32 [V, 3], triangles int32 [T, 3], 0-based) as numpy arrays: the reader the mesh metrics need
+    (rfuse/mesh_metrics.py compute_metrics; the reference goes through trimesh.load_mesh).  Reads 'v x y z [w]' and 'f ...' lines; a face index may
+    be 'a', 'a/b', 'a//c' or 'a/b/c' (the vertex index is the first field), 1-based, negative = counted from the last vertex read so far; polygons
+    are fan-triangulated from their first corner.  Every other line is ignored.  Round-trips ``export_obj`` (to the six decimals it writes)."""
+    verts, tris = [], []
+    with open(path) as f:
+        for no, line in enumerate(f, 1):
+            parts = line.split()
+            if not parts:
+                continue
+            if parts[0] == 'v':
+                if len(parts) < 4:
+                    raise ValueError('%s:%d: a vertex needs three coordinates' % (path, no))
+                verts.append((float(parts[1]), float(parts[2]), float(parts[3])))
+            elif parts[0] == 'f':
+                if len(parts) < 4:
+                    raise ValueError('%s:%d: a face needs three corners' % (path, no))
+                idx = [int(q.split('/')[0]) for q in parts[1:]]
+                idx = [i - 1 if i > 0 else len(verts) + i for i in idx]
+                if 0 in [int(q.split('/')[0]) for q in parts[1:]]:
+                    raise ValueError('%s:%d: face indices are 1-based' % (path, no))
+                tris += [(idx[0], idx[k], idx[k + 1]) for k in range(1, len(idx) - 1)]
+    v = np.array(verts, dtype=np.float64).reshape(-1, 3).astype(np.float32)
+    t = np.array(tris, dtype=np.int64).reshape(-1, 3)
+    if len(t) and (t.min() < 0 or t.max() >= len(v)):
+        raise ValueError('%s: a face refers to vertex %d of %d' % (path, int(t.max() if t.max() >= len(v) else t.min()) + 1, len(v)))
+    return v, t.astype(np.int32)
+
+
 def visualize_sdf_as_mesh(sdf, output_path, level=0.75, scale_factor=1):
     """reference util/visualization.py:34-37, same arguments"""
     vertices, triangles = marching_cubes(sdf, level)
