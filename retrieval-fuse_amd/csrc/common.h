@@ -76,6 +76,14 @@ static inline int rf_resident_wgs() {
 }
 static inline int rf_persistent_wgs() { return rf_resident_wgs() * RF_PERSIST_ROUNDS; }
 
+// Workgroups are handed to the 8 XCDs round-robin by linear id, each XCD with its own L2.  Tiles that split a sample
+// (8-voxel = 32-byte row pieces of 64..512-byte rows) would then share every cache line across XCDs: partial-line writes
+// that no L2 can merge and 128-byte fills for 32 bytes of use.  Remap so that XCD k walks a contiguous range of tiles.
+__device__ __forceinline__ unsigned rf_xcd_contiguous(unsigned b, unsigned g) {
+    const unsigned per = g >> 3, rem = g & 7u, k = b & 7u;
+    return k * per + (k < rem ? k : rem) + (b >> 3);
+}
+
 // wave64 sum reduction; result valid in every lane
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
@@ -119,4 +127,13 @@ __device__ __forceinline__ float4 gn_affine(double mean, double rstd, float gamm
     const double sc = (double)gamma * rstd;
     const float center = (float)mean;
     return make_float4(center, (float)sc, (float)((double)beta - (mean - (double)center) * sc), 0.f);
+}
+// THE hand-over from (sum, sum of squares) of `count` values to that triple, float64 throughout: biased variance, clamped at 0 (cancellation
+// can leave it just below), rstd = 1 / sqrt(var + eps).  Every route that derives a GroupNorm from statistics goes through here -- the "bit-equal
+// between routes" tests hold only as long as there is one definition.  (Written out instead, each with its reason: k_conv3_up_split_pp, k_conv3_split's pre-split epilogue, conv3d_backward.hip.)
+__device__ __forceinline__ float4 rf_gn_triple(double sm, double sq, double count, double eps, float gamma, float beta) {
+    const double mean = sm / count;
+    double var = sq / count - mean * mean;
+    if (var < 0.0) var = 0.0;
+    return gn_affine(mean, 1.0 / sqrt(var + eps), gamma, beta);
 }

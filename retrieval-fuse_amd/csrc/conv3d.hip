@@ -115,11 +115,7 @@ __global__ void k_gn_finalize(const double2* __restrict__ part, int n, int C, in
         a += p.x;
         b += p.y;
     }
-    const double mean = a / count;
-    double var = b / count - mean * mean;
-    if (var < 0.0) var = 0.0;
-    const double rstd = 1.0 / sqrt(var + eps);
-    affine[i] = gn_affine(mean, rstd, gamma[c], beta[c]);
+    affine[i] = rf_gn_triple(a, b, count, eps, gamma[c], beta[c]);
 }
 
 static int gn_slices(size_t group_elems) {
@@ -358,11 +354,7 @@ __global__ __launch_bounds__(256) void k_gn_from_stats(const double2* __restrict
         sm = wave_sum(sm);
         sq = wave_sum(sq);
     }
-    const double mean = sm / count;
-    double var = sq / count - mean * mean;
-    if (var < 0.0) var = 0.0;
-    const double rstd = 1.0 / sqrt(var + eps);
-    for (int c = ca + lane; c < cb; c += LPU) affine[(size_t)nn * C + c] = gn_affine(mean, rstd, gamma[c], beta[c]);
+    for (int c = ca + lane; c < cb; c += LPU) affine[(size_t)nn * C + c] = rf_gn_triple(sm, sq, count, eps, gamma[c], beta[c]);
 }
 
 extern "C" int rf_gn_from_stats(const double* stats0, int c0, int tiles0, const double* stats1, int c1, int tiles1, int n, int edge,

@@ -277,7 +277,7 @@ __global__ __launch_bounds__(64) void k_gnb_finalize(const double4* __restrict__
             for (int k = 0; k < 64 && k0 + k < cpg; ++k) { S += ch[k].x; Q += ch[k].y; }
         __syncthreads();
     }
-    if (tid == 0) {
+    if (tid == 0) {                                                 // not rf_gn_triple: the backward needs mean and rstd themselves, not the forward's triple
         const double mean = S / m;
         double var = Q / m - mean * mean;
         if (var < 0.0) var = 0.0;

@@ -14,6 +14,7 @@
 // before the MFMAs of the current chunk and normalised + split + written to the other buffer after them; one barrier per chunk.
 // B operands (weights): f16 fragment image from rf_conv3_split_pack_weight ([chunk][k-step][n-block][h|l][lane][8 halves]), L2-resident,
 // global -> VGPR one k-step ahead.  Register use is small (NB 1: 32 accumulator VGPRs), two workgroups per CU.
+// Pre-split output (whole 8^3 samples): the hand-over epilogue of conv_split_common.h; the triple from the sums is common.h:rf_gn_triple.
 #include "common.h"
 #include "conv_box.h"
 #include "conv_split_common.h"
@@ -308,22 +309,16 @@ __global__ __launch_bounds__(512, WPS) void k_conv3_split(ConvArgs a, SplitPreOu
             double2* chst = reinterpret_cast<double2*>(lds + CS_PO_STATS);
             float4* trip = reinterpret_cast<float4*>(lds + CS_PO_TRIPLES);
             {
-                const int co = tid >> 5, part = tid & 31;               // 32 threads per cout, 16 values each, then a butterfly (fixed order)
-                double sm = 0.0, sq = 0.0;
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    const float v = e[co * CS_PO_STRIDE + part + 32 * i];
-                    sm += (double)v; sq += (double)v * v;
-                }
-#pragma unroll
-                for (int msk = 1; msk < 32; msk <<= 1) { sm += __shfl_xor(sm, msk, 64); sq += __shfl_xor(sq, msk, 64); }
+                const int co = tid >> 5, part = tid & 31;               // 32 threads per cout
+                const double2 s = rf_tile_channel_sums<CS_PO_STRIDE, 32>(e, co, part, true);
                 if (part == 0) {
-                    chst[co] = make_double2(sm, sq);
-                    if (a.stats && cob + co < a.cout) a.stats[(size_t)n0 * a.cout + cob + co] = make_double2(sm, sq);
+                    chst[co] = s;
+                    if (a.stats && cob + co < a.cout) a.stats[(size_t)n0 * a.cout + cob + co] = s;
                 }
             }
             __syncthreads();
-            if (tid < a.cout) {                                        // as rf_gn_from_stats: group sums in channel order, float64
+            if (tid < a.cout) {
+                // rf_group_triple written out: through rf_gn_triple the PRE instance of this kernel spills one more SGPR (5 against 4); keep the two in step
                 const int cpg = a.cout / po.groups, ca = (tid / cpg) * cpg;
                 double sm = 0.0, sq = 0.0;
                 for (int c = ca; c < ca + cpg; ++c) { sm += chst[c].x; sq += chst[c].y; }
@@ -333,19 +328,7 @@ __global__ __launch_bounds__(512, WPS) void k_conv3_split(ConvArgs a, SplitPreOu
                 trip[tid] = gn_affine(mean, 1.0 / sqrt(var + (double)po.eps), po.gamma[tid], po.beta[tid]);
             }
             __syncthreads();
-            h8* __restrict__ o = po.out + (size_t)n0 * (a.cout >> 3) * 2 * 512 + tid;
-            for (int sg = 0; sg < (a.cout >> 3); ++sg) {
-                float y[8];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const float4 t4 = trip[sg * 8 + j];
-                    y[j] = fmaf(e[(sg * 8 + j) * CS_PO_STRIDE + tid] - t4.x, t4.y, t4.z);
-                }
-                h8 h, l;
-                rf_split8(y, h, l);
-                o[(size_t)sg * 2 * 512] = h;
-                o[(size_t)sg * 2 * 512 + 512] = l;
-            }
+            rf_presplit_store<512>(po.out + (size_t)n0 * (a.cout >> 3) * 2 * 512 + tid, a.cout >> 3, trip, [&](int c) { return e[c * CS_PO_STRIDE + tid]; });
             return;
         }
         if (po.pw_out) {
@@ -549,10 +532,7 @@ __global__ __launch_bounds__(512, 4) void k_conv3_cin1_presplit(Cin1PreArgs a) {
     {
         double sm = 0.0, sq = 0.0;
         for (int w = 0; w < 8; ++w) { sm += red[2 * w]; sq += red[2 * w + 1]; }
-        const double mean = sm / VOL;
-        double var = sq / VOL - mean * mean;
-        if (var < 0.0) var = 0.0;
-        af = gn_affine(mean, 1.0 / sqrt(var + a.eps_in), a.gamma_in[0], a.beta_in[0]);
+        af = rf_gn_triple(sm, sq, VOL, a.eps_in, a.gamma_in[0], a.beta_in[0]);
     }
     __syncthreads();                                                // red is reused for the output statistics
 #pragma unroll
@@ -625,10 +605,7 @@ __global__ __launch_bounds__(512, 4) void k_conv3_cin1_presplit(Cin1PreArgs a) {
         double sm = 0.0, sq = 0.0;
         for (int c = g0; c < g0 + a.cpg; ++c)
             for (int w = 0; w < 8; ++w) { sm += red[w * 16 + 2 * c]; sq += red[w * 16 + 2 * c + 1]; }
-        const double count = (double)a.cpg * VOL, mean = sm / count;
-        double var = sq / count - mean * mean;
-        if (var < 0.0) var = 0.0;
-        nxt[tid] = gn_affine(mean, 1.0 / sqrt(var + a.eps), a.gamma[tid], a.beta[tid]);
+        nxt[tid] = rf_gn_triple(sm, sq, (double)a.cpg * VOL, a.eps, a.gamma[tid], a.beta[tid]);
     }
     __syncthreads();
     // normalise + split on cout PAIRS: the 2^-4 activation scale is folded into the triple (exact: a power of two commutes with the fma's rounding), the

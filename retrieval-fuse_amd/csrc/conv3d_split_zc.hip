@@ -15,6 +15,7 @@
 //  * x-adjacent box PAIRS share one epilogue: the pooled rows of both boxes go through an LDS tile and leave as 128-byte runs (the box kernel wrote
 //    16-byte fragments: 4.2x write amplification on the pooled-only layer); GroupNorm statistics are accumulated per wave over the eight
 //    boxes of a sample and reduced once per sample (stats_tiles = 1).
+// Both kernels hand a whole sample over pre-split with the epilogue pieces of conv_split_common.h (triple: common.h:rf_gn_triple).
 #include "common.h"
 #include "conv_box.h"
 #include "conv_split_common.h"
@@ -295,31 +296,12 @@ __global__ __launch_bounds__(512, 4) void k_conv3_split_zc(ConvArgs a, SplitPreO
             // atomic loads).  NOT a device-scope release / acquire fence pair: that writes back and invalidates whole caches -- measured 0.57 -> 3.4 ms per launch
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             lds_barrier();
-            if (tv < a.cout) {                                        // as rf_gn_from_stats: group sums in channel order, float64
-                const int cpg = a.cout / po.groups, c0 = (tv / cpg) * cpg;
-                double sm = 0.0, sq = 0.0;
-                for (int c = c0; c < c0 + cpg; ++c) { sm += chst[c].x; sq += chst[c].y; }
-                const double count = (double)cpg * PVOL, mean = sm / count;
-                double var = sq / count - mean * mean;
-                if (var < 0.0) var = 0.0;
-                trip[tv] = gn_affine(mean, 1.0 / sqrt(var + (double)po.eps), po.gamma[tv], po.beta[tv]);
-            }
+            if (tv < a.cout) trip[tv] = rf_group_triple(chst, tv, a.cout / po.groups, PVOL, po.eps, po.gamma, po.beta);
             lds_barrier();
             const int n0 = boxA >> 3;
             const float* pv = a.pool_out + (size_t)blockIdx.x * a.cout * PVOL + (unsigned)tv;       // this workgroup's scratch slot (see the pooled stores)
-            h8* __restrict__ o = po.out + (size_t)n0 * (a.cout >> 3) * 2 * PVOL + (unsigned)tv;
-            for (int sg = 0; sg < (a.cout >> 3); ++sg) {
-                float y[8];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const float4 t4 = trip[sg * 8 + j];
-                    y[j] = fmaf(__hip_atomic_load(pv + (sg * 8 + j) * PVOL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - t4.x, t4.y, t4.z);
-                }
-                h8 h, l;
-                rf_split8(y, h, l);
-                o[(size_t)sg * 2 * PVOL] = h;
-                o[(size_t)sg * 2 * PVOL + PVOL] = l;
-            }
+            rf_presplit_store<PVOL>(po.out + (size_t)n0 * (a.cout >> 3) * 2 * PVOL + (unsigned)tv, a.cout >> 3, trip,
+                                    [&](int c) { return __hip_atomic_load(pv + c * PVOL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); });
         }
         stage_store(st, bufB);                                      // the next pair's box A into the buffer box B has left
         lds_barrier();                                              // 3: ... complete; the tile has been read
@@ -643,50 +625,24 @@ __global__ __launch_bounds__(512, 4) void k_conv3_split_zcm(ConvArgs a, SplitPre
                     (po.pw_out + (size_t)n0 * vol)[(unsigned)(((z0 + z) * edge + (y0 + y)) * edge + x0 + x)] = (tanhf(accp) + po.post_add) * po.post_mul;
                 } else {
                     // pre-split output (whole 8^3 samples): statistics of the sample -> the next layer's GroupNorm triples -> normalise, split, slots
-                    // (the arithmetic of k_conv3_split's pre-split epilogue, conv3d_split.hip)
+                    // (the hand-over epilogue of conv_split_common.h, as k_conv3_split's)
                     double2* chst = reinterpret_cast<double2*>(lds + ZM_SCRATCH);
                     float4* trip = reinterpret_cast<float4*>(lds + ZM_SCRATCH + 256);
                     int tv = tid;
                     asm volatile("" : "+v"(tv));                      // (keeps the addresses below out of the chunk loop's preheader, see EPI 0)
                     {
-                        const int co = tv >> 5, part = tv & 31;       // 32 threads per cout, 16 values each, then a butterfly (fixed order)
-                        double sm = 0.0, sq = 0.0;
-#pragma unroll
-                        for (int i = 0; i < 16; ++i) {
-                            const float v = e[co * ZM_TILE_STRIDE + part + 32 * i];
-                            sm += (double)v; sq += (double)v * v;
-                        }
-#pragma unroll
-                        for (int msk = 1; msk < 32; msk <<= 1) { sm += __shfl_xor(sm, msk, 64); sq += __shfl_xor(sq, msk, 64); }
+                        const int co = tv >> 5, part = tv & 31;       // 32 threads per cout
+                        const double2 s = rf_tile_channel_sums<ZM_TILE_STRIDE, 32>(e, co, part, true);
                         if (part == 0) {
-                            chst[co] = make_double2(sm, sq);
-                            if (a.stats && co < a.cout) a.stats[(size_t)n0 * a.cout + co] = make_double2(sm, sq);
+                            chst[co] = s;
+                            if (a.stats && co < a.cout) a.stats[(size_t)n0 * a.cout + co] = s;
                         }
                     }
                     lds_barrier();
-                    if (tv < a.cout) {                                // as rf_gn_from_stats: group sums in channel order, float64
-                        const int cpg = a.cout / po.groups, c0 = (tv / cpg) * cpg;
-                        double sm = 0.0, sq = 0.0;
-                        for (int c = c0; c < c0 + cpg; ++c) { sm += chst[c].x; sq += chst[c].y; }
-                        const double count = (double)cpg * 512.0, mean = sm / count;
-                        double var = sq / count - mean * mean;
-                        if (var < 0.0) var = 0.0;
-                        trip[tv] = gn_affine(mean, 1.0 / sqrt(var + (double)po.eps), po.gamma[tv], po.beta[tv]);
-                    }
+                    if (tv < a.cout) trip[tv] = rf_group_triple(chst, tv, a.cout / po.groups, 512.0, po.eps, po.gamma, po.beta);
                     lds_barrier();
-                    h8* __restrict__ o = po.out + (size_t)n0 * (a.cout >> 3) * 2 * 512 + (unsigned)tv;
-                    for (int sg = 0; sg < (a.cout >> 3); ++sg) {
-                        float y[8];
-#pragma unroll
-                        for (int j = 0; j < 8; ++j) {
-                            const float4 t4 = trip[sg * 8 + j];
-                            y[j] = fmaf(e[(sg * 8 + j) * ZM_TILE_STRIDE + tv] - t4.x, t4.y, t4.z);
-                        }
-                        h8 h, l;
-                        rf_split8(y, h, l);
-                        o[(size_t)sg * 2 * 512] = h;
-                        o[(size_t)sg * 2 * 512 + 512] = l;
-                    }
+                    rf_presplit_store<512>(po.out + (size_t)n0 * (a.cout >> 3) * 2 * 512 + (unsigned)tv, a.cout >> 3, trip,
+                                           [&](int c) { return e[c * ZM_TILE_STRIDE + tv]; });
                 }
             }
         }

@@ -22,9 +22,8 @@
 // instantiated per pz for that.
 // Epilogue: accumulators -> ReLU -> LDS tile [cout][8^3] (rows of 517 floats: conflict-free scalar writes) -> 256-byte row stores; GroupNorm
 // statistics of the output (float64, fixed order) for the next layer -- or (rf_conv3d_up_split_presplit) the next layer's GroupNorm applied on
-// the spot and the output written pre-split.
-#include "common.h"
-#include "split_operand.h"
+// the spot and the output written pre-split (the hand-over epilogue of conv_split_common.h).
+#include "conv_split_common.h"
 #include <type_traits>
 
 namespace {
@@ -39,6 +38,7 @@ constexpr int US_LDS_BYTES = US_B_OFF + US_MAX_CGB * 2 * US_B_PLANE;      // 132
 constexpr int US_PRE_STATS = US_LDS_BYTES, US_PRE_TRIPLES = US_PRE_STATS + 64 * 16;     // pre-split epilogue: per-channel (sum, sum of squares), then triples
 constexpr int US_LDS_ALLOC = US_PRE_TRIPLES + 64 * 16;                                     // 134,656
 constexpr int US_T_STRIDE = 517;                                 // epilogue tile row (floats) of the whole-sample kernel: odd (bank-conflict-free scalar writes)
+constexpr int UB_E_STRIDE = 516;                                 // ... of the box kernels: a multiple of 4 (16-byte row reads)
 constexpr bool US_ZSKIP = true;
 static_assert(64 * US_T_STRIDE * 4 <= US_LDS_BYTES, "epilogue tile must fit");
 }   // namespace
@@ -127,6 +127,89 @@ struct UpSplitArgs {
     // + (x >> 1) instead of z 64 + y 8 + x -- so that a wave, which owns one output parity, stores 256-byte runs (RF_PRESPLIT_PARITY_MAJOR)
     int pre_pm;
 };
+
+// ------------------------------------------------------------------------------------- pieces that the kernels below compose
+// Wave = output parity (pz, py, px), m-block m = z pair m, lane = (cout of the n-block = lane & 15, y pair = lane >> 4; r = x pair): the accumulators, joined and
+// ReLU'd, into the LDS tile [cout][z][y][x] of the 8^3 sample / box (rows of STRIDE floats)
+template <int NB, int STRIDE>
+__device__ __forceinline__ void us_acc_to_tile(float* e, const f32x4 (&hi)[4][NB], const f32x4 (&lo)[4][NB], int lane, int pz, int py, int px) {
+    const int col = lane & 15, yj = lane >> 4;
+#pragma unroll
+    for (int m = 0; m < 4; ++m)
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int lin = (2 * m + pz) * 64 + (2 * yj + py) * 8 + 2 * r + px;
+                e[(nb * 16 + col) * STRIDE + lin] = rf_relu(rf_split_join(hi[m][nb][r], lo[m][nb][r]));
+            }
+}
+
+// The box kernels: workgroup -> (sample n, box `tile` of the sample at (z0, y0, x0)) of an edge^3 volume with tpe boxes per edge, in the XCD-contiguous
+// order (common.h): neighbouring boxes share halo voxels and output cache lines
+struct UsBox { int n, tile, z0, y0, x0; };
+__device__ __forceinline__ UsBox us_box_decode(int tpe) {
+    int t = (int)rf_xcd_contiguous(blockIdx.x, gridDim.x);
+    UsBox b;
+    b.tile = t % (tpe * tpe * tpe);
+    b.x0 = (t % tpe) * 8; t /= tpe;
+    b.y0 = (t % tpe) * 8; t /= tpe;
+    b.z0 = (t % tpe) * 8; t /= tpe;
+    b.n = t;
+    return b;
+}
+
+// low-res halo boxes [6][6][6] of that box, all nB channel groups: thread = (channel group, halo voxel), 216 voxels per group; normalised by aff (the
+// triples of src1's channels), split, to img [group][h | l][slot]; outside the volume: the zero padding of the NORMALISED tensor
+__device__ __forceinline__ void us_stage_lowres(unsigned char* img, const float* src1, const float4* __restrict__ aff, int n, int c1, int nB, int half,
+                                                int z0, int y0, int x0, int tid) {
+    const size_t hvol = (size_t)half * half * half;
+    for (int u = tid; u < nB * US_BSLOTS; u += 512) {
+        const int cg = u / US_BSLOTS, v = u % US_BSLOTS;
+        const int hz = v / US_BZ, hy = (v / US_BY) % 6, hx = v % 6;
+        const int z = (z0 >> 1) + hz - 1, y = (y0 >> 1) + hy - 1, x = (x0 >> 1) + hx - 1;
+        const bool in = (unsigned)z < (unsigned)half && (unsigned)y < (unsigned)half && (unsigned)x < (unsigned)half;
+        float yv[8];
+        const float* __restrict__ sp = src1 + ((size_t)n * c1 + cg * 8) * hvol + (in ? ((size_t)z * half + y) * half + x : 0);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const float4 af = aff[cg * 8 + j];
+            yv[j] = in ? fmaf(sp[(size_t)j * hvol] - af.x, af.y, af.z) : 0.f;
+        }
+        h8 h, l;
+        rf_split8(yv, h, l);
+        unsigned char* p = img + cg * 2 * US_B_PLANE + v * 16;
+        *reinterpret_cast<h8*>(p) = h;
+        *reinterpret_cast<h8*>(p + US_B_PLANE) = l;
+    }
+}
+
+// `rows` couts of the box tile -> NCDHW: o = (first cout, box origin); a float4 = half a box row, index l4 = (z, y, half row)
+__device__ __forceinline__ void us_store_box_rows(float* __restrict__ o, const float* e, int rows, size_t vol, int edge, int tid) {
+    for (int q = tid; q < rows * 128; q += 512) {
+        const int co = q >> 7, l4 = q & 127;
+        const int z = l4 >> 4, y = (l4 >> 1) & 7, xh = l4 & 1;
+        *reinterpret_cast<float4*>(o + (size_t)co * vol + ((size_t)z * edge + y) * edge + xh * 4) = *reinterpret_cast<const float4*>(e + co * UB_E_STRIDE + l4 * 4);
+    }
+}
+
+// (sum, sum of squares) of one cout's box: eight threads (`part`) sum 64 consecutive values each (float64), then the eight partial sums in a fixed order
+__device__ __forceinline__ double2 us_box_channel_sums(const float* e, int co, int part, bool live) {
+    double sm = 0.0, sq = 0.0;
+    if (live) {
+#pragma unroll 4
+        for (int i = 0; i < 16; ++i) {
+            const float4 v = *reinterpret_cast<const float4*>(e + co * UB_E_STRIDE + (part * 16 + i) * 4);
+            sm += (double)v.x; sq += (double)v.x * v.x;
+            sm += (double)v.y; sq += (double)v.y * v.y;
+            sm += (double)v.z; sq += (double)v.z * v.z;
+            sm += (double)v.w; sq += (double)v.w * v.w;
+        }
+    }
+#pragma unroll
+    for (int msk = 1; msk < 8; msk <<= 1) { sm += __shfl_xor(sm, msk, 64); sq += __shfl_xor(sq, msk, 64); }
+    return make_double2(sm, sq);
+}
 
 template <int NB>
 __global__ __launch_bounds__(512, 2) void k_conv3_up_split(UpSplitArgs a) {
@@ -342,18 +425,7 @@ __global__ __launch_bounds__(512, 2) void k_conv3_up_split(UpSplitArgs a) {
     int te = tid;
     asm volatile("" : "+v"(te));
     float* e = reinterpret_cast<float*>(lds);
-    {
-        const int col = te & 15, yj = (te >> 4) & 3;
-#pragma unroll
-        for (int m = 0; m < 4; ++m)
-#pragma unroll
-            for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int lin = (2 * m + pz) * 64 + (2 * yj + py) * 8 + 2 * r + px;
-                    e[(nb * 16 + col) * US_T_STRIDE + lin] = rf_relu(rf_split_join(hi[m][nb][r], lo[m][nb][r]));
-                }
-    }
+    us_acc_to_tile<NB, US_T_STRIDE>(e, hi, lo, te & 63, pz, py, px);
     __syncthreads();
     const int cout = a.cout;
     if (a.pre_out) {
@@ -361,46 +433,17 @@ __global__ __launch_bounds__(512, 2) void k_conv3_up_split(UpSplitArgs a) {
         double2* chst = reinterpret_cast<double2*>(lds + US_PRE_STATS);
         float4* trip = reinterpret_cast<float4*>(lds + US_PRE_TRIPLES);
         {
-            const int co = te >> 3, part = te & 7;
-            double sm = 0.0, sq = 0.0;
-            if (co < cout) {
-#pragma unroll 8
-                for (int i = 0; i < 64; ++i) {
-                    const float v = e[co * US_T_STRIDE + part + 8 * i];
-                    sm += (double)v; sq += (double)v * v;
-                }
-            }
-#pragma unroll
-            for (int msk = 1; msk < 8; msk <<= 1) { sm += __shfl_xor(sm, msk, 64); sq += __shfl_xor(sq, msk, 64); }
-            if (part == 0 && co < cout) {
-                chst[co] = make_double2(sm, sq);
-                if (a.stats) a.stats[(size_t)n * cout + co] = make_double2(sm, sq);
+            const int sco = te >> 3, spart = te & 7;                // eight threads per cout
+            const double2 s = rf_tile_channel_sums<US_T_STRIDE, 8>(e, sco, spart, sco < cout);
+            if (spart == 0 && sco < cout) {
+                chst[sco] = s;
+                if (a.stats) a.stats[(size_t)n * cout + sco] = s;
             }
         }
         __syncthreads();
-        if (te < cout) {                                             // as rf_gn_from_stats: group sums in channel order, float64
-            const int cpg = cout / a.ngroups, ca = (te / cpg) * cpg;
-            double sm = 0.0, sq = 0.0;
-            for (int c = ca; c < ca + cpg; ++c) { sm += chst[c].x; sq += chst[c].y; }
-            const double count = (double)cpg * 512.0, mean = sm / count;
-            double var = sq / count - mean * mean;
-            if (var < 0.0) var = 0.0;
-            trip[te] = gn_affine(mean, 1.0 / sqrt(var + (double)a.neps), a.ngamma[te], a.nbeta[te]);
-        }
+        if (te < cout) trip[te] = rf_group_triple(chst, te, cout / a.ngroups, 512.0, a.neps, a.ngamma, a.nbeta);
         __syncthreads();
-        h8* __restrict__ po = a.pre_out + (size_t)n * (cout >> 3) * 2 * 512 + te;
-        for (int sg = 0; sg < (cout >> 3); ++sg) {
-            float y[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float4 t4 = trip[sg * 8 + j];
-                y[j] = fmaf(e[(sg * 8 + j) * US_T_STRIDE + te] - t4.x, t4.y, t4.z);
-            }
-            h8 h, l;
-            rf_split8(y, h, l);
-            po[(size_t)sg * 2 * 512] = h;
-            po[(size_t)sg * 2 * 512 + 512] = l;
-        }
+        rf_presplit_store<512>(a.pre_out + (size_t)n * (cout >> 3) * 2 * 512 + te, cout >> 3, trip, [&](int c) { return e[c * US_T_STRIDE + te]; });
         return;
     }
     float* __restrict__ o = a.out + (size_t)n * cout * 512;
@@ -409,19 +452,9 @@ __global__ __launch_bounds__(512, 2) void k_conv3_up_split(UpSplitArgs a) {
 #pragma unroll 4
     for (int co = 0; co < cout; ++co) o[(size_t)co * 512 + te] = e[co * US_T_STRIDE + te];
     if (a.stats) {
-        // per cout: eight threads sum 64 values each (voxels part, part + 8, ...; float64), then the eight partial sums in a fixed order
-        const int co = te >> 3, part = te & 7;
-        double sm = 0.0, sq = 0.0;
-        if (co < cout) {
-#pragma unroll 8
-            for (int i = 0; i < 64; ++i) {
-                const float v = e[co * US_T_STRIDE + part + 8 * i];
-                sm += (double)v; sq += (double)v * v;
-            }
-        }
-#pragma unroll
-        for (int msk = 1; msk < 8; msk <<= 1) { sm += __shfl_xor(sm, msk, 64); sq += __shfl_xor(sq, msk, 64); }
-        if (part == 0 && co < cout) a.stats[(size_t)n * cout + co] = make_double2(sm, sq);
+        const int sco = te >> 3, spart = te & 7;
+        const double2 s = rf_tile_channel_sums<US_T_STRIDE, 8>(e, sco, spart, sco < cout);
+        if (spart == 0 && sco < cout) a.stats[(size_t)n * cout + sco] = s;
     }
     };   // run
     if (pz == 0) run(std::integral_constant<int, 0>{});
@@ -875,6 +908,7 @@ __global__ __launch_bounds__(512, 2) void k_conv3_up_split_pp(UpSplitArgs a) {
             const int cbeg = (te / cpg) * cpg;
             double sm = 0.0, sq = 0.0;
             for (int c = cbeg; c < cbeg + cpg; ++c) { sm += chs[c].x; sq += chs[c].y; }
+            // not rf_gn_triple: 1 / count and eps come from scalar-pinned operands and the rstd is the rsq + Newton form below
             const double icnt = __hiloint2double(icnt_hi, icnt_lo), mean = sm * icnt;
             double var = sq * icnt - mean * mean;
             if (var < 0.0) var = 0.0;
@@ -1162,9 +1196,6 @@ __global__ __launch_bounds__(512, NB >= 3 ? 2 : 4) void k_conv3_up_split_s4(UpSp
 // m-block m = z pair m; per channel group two k-steps (tz = 0 / 1), lane group = (ty, tx).  With 16 input channels that is 48 MFMAs per wave:
 // the kernel is its staging (216 x c1 values in) and its epilogue (512 x cout values out + statistics), and small enough in registers and
 // LDS (33 KB) for four workgroups per CU to overlap them.
-namespace {
-constexpr int UB_E_STRIDE = 516;
-}
 template <int NB>
 __global__ __launch_bounds__(512, 4) void k_conv3_up_split_box(UpSplitArgs a, int edge) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
@@ -1172,36 +1203,8 @@ __global__ __launch_bounds__(512, 4) void k_conv3_up_split_box(UpSplitArgs a, in
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int pz = wave >> 2, py = (wave >> 1) & 1, px = wave & 1;
     const int c1 = a.c1, nB = c1 >> 3, half = edge >> 1, tpe = edge >> 3;
-    // XCD-contiguous box order (conv_box.h): neighbouring boxes share halo voxels and output cache lines
-    const unsigned g_ = gridDim.x, per = g_ >> 3, rem = g_ & 7u, kx = blockIdx.x & 7u;
-    int t = (int)(kx * per + (kx < rem ? kx : rem) + (blockIdx.x >> 3));
-    const int tile = t % (tpe * tpe * tpe);
-    const int x0 = (t % tpe) * 8; t /= tpe;
-    const int y0 = (t % tpe) * 8; t /= tpe;
-    const int z0 = (t % tpe) * 8; t /= tpe;
-    const int n = t;
-    const float4* __restrict__ aff = a.affine + (size_t)n * c1;
-    const size_t hvol = (size_t)half * half * half;
-
-    // ---- stage: thread = (channel group, halo voxel); 216 voxels per group
-    for (int u = tid; u < nB * US_BSLOTS; u += 512) {
-        const int cg = u / US_BSLOTS, v = u % US_BSLOTS;
-        const int hz = v / US_BZ, hy = (v / US_BY) % 6, hx = v % 6;
-        const int z = (z0 >> 1) + hz - 1, y = (y0 >> 1) + hy - 1, x = (x0 >> 1) + hx - 1;
-        const bool in = (unsigned)z < (unsigned)half && (unsigned)y < (unsigned)half && (unsigned)x < (unsigned)half;
-        float yv[8];
-        const float* __restrict__ sp = a.src1 + ((size_t)n * c1 + cg * 8) * hvol + (in ? ((size_t)z * half + y) * half + x : 0);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const float4 af = aff[cg * 8 + j];
-            yv[j] = in ? fmaf(sp[(size_t)j * hvol] - af.x, af.y, af.z) : 0.f;       // zero padding of the NORMALISED tensor
-        }
-        h8 h, l;
-        rf_split8(yv, h, l);
-        unsigned char* p = lds + cg * 2 * US_B_PLANE + v * 16;
-        *reinterpret_cast<h8*>(p) = h;
-        *reinterpret_cast<h8*>(p + US_B_PLANE) = l;
-    }
+    const auto [n, tile, z0, y0, x0] = us_box_decode(tpe);
+    us_stage_lowres(lds, a.src1, a.affine + (size_t)n * c1, n, c1, nB, half, z0, y0, x0, tid);
 
     const int g = lane >> 4, rj = (lane >> 2) & 3, ri = lane & 3;
     const int bbase = (pz * US_BZ + (rj + py + (g >> 1)) * US_BY + (ri + px + (g & 1))) * 16;        // + (m + tz) BZ
@@ -1233,18 +1236,7 @@ __global__ __launch_bounds__(512, 4) void k_conv3_up_split_box(UpSplitArgs a, in
 
     // ---- epilogue: relu(hi + lo / 2^11) -> LDS tile [cout][z][y][x] of the box -> float4 half rows, statistics of the box per cout
     float* e = reinterpret_cast<float*>(lds);
-    {
-        const int col = lane & 15, yj = lane >> 4;
-#pragma unroll
-        for (int m = 0; m < 4; ++m)
-#pragma unroll
-            for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int lin = (2 * m + pz) * 64 + (2 * yj + py) * 8 + 2 * r + px;
-                    e[(nb * 16 + col) * UB_E_STRIDE + lin] = rf_relu(rf_split_join(hi[m][nb][r], lo[m][nb][r]));
-                }
-    }
+    us_acc_to_tile<NB, UB_E_STRIDE>(e, hi, lo, lane, pz, py, px);
     __syncthreads();
     const int cout = a.cout;
     const size_t vol = (size_t)edge * edge * edge;
@@ -1259,29 +1251,12 @@ __global__ __launch_bounds__(512, 4) void k_conv3_up_split_box(UpSplitArgs a, in
                 make_float4(ep[0], ep[UB_E_STRIDE], ep[2 * UB_E_STRIDE], ep[3 * UB_E_STRIDE]);
         }
     }
-    float* __restrict__ o = a.out + (size_t)n * cout * vol + ((size_t)z0 * edge + y0) * edge + x0;
-    for (int q = tid; q < (a.out_ch8 ? 0 : cout * 128); q += 512) {
-        const int co = q >> 7, l4 = q & 127;                          // l4: float4 index inside the box: (z, y, half row)
-        const int z = l4 >> 4, y = (l4 >> 1) & 7, xh = l4 & 1;
-        *reinterpret_cast<float4*>(o + (size_t)co * vol + ((size_t)z * edge + y) * edge + xh * 4) = *reinterpret_cast<const float4*>(e + co * UB_E_STRIDE + l4 * 4);
-    }
+    us_store_box_rows(a.out + (size_t)n * cout * vol + ((size_t)z0 * edge + y0) * edge + x0, e, a.out_ch8 ? 0 : cout, vol, edge, tid);
     if (a.stats) {
         const int tiles = tpe * tpe * tpe;
         const int co = tid >> 3, part = tid & 7;
-        double sm = 0.0, sq = 0.0;
-        if (co < cout) {
-#pragma unroll 4
-            for (int i = 0; i < 16; ++i) {
-                const float4 v = *reinterpret_cast<const float4*>(e + co * UB_E_STRIDE + (part * 16 + i) * 4);
-                sm += (double)v.x; sq += (double)v.x * v.x;
-                sm += (double)v.y; sq += (double)v.y * v.y;
-                sm += (double)v.z; sq += (double)v.z * v.z;
-                sm += (double)v.w; sq += (double)v.w * v.w;
-            }
-        }
-#pragma unroll
-        for (int msk = 1; msk < 8; msk <<= 1) { sm += __shfl_xor(sm, msk, 64); sq += __shfl_xor(sq, msk, 64); }
-        if (part == 0 && co < cout) a.stats[((size_t)n * cout + co) * tiles + tile] = make_double2(sm, sq);
+        const double2 s = us_box_channel_sums(e, co, part, co < cout);
+        if (part == 0 && co < cout) a.stats[((size_t)n * cout + co) * tiles + tile] = s;
     }
 }
 
@@ -1293,7 +1268,7 @@ __global__ __launch_bounds__(512, 4) void k_conv3_up_split_box(UpSplitArgs a, in
 // drained while the next voxels are in flight.  Two barriers per box:
 //     MFMA(i) | A | tile(i) <- accumulators, image(i + 1) <- registers | B | request box i + 2, store tile(i), statistics(i)
 // Results are those of k_conv3_up_split_box bit for bit (same products, same accumulation order, same statistics order).
-// Measured (tools/upbox_bench.py, tools/upbox_ablation.py; 32 chunks): 0.315 -> 0.25 ms alone.  Without the voxel loads 0.17, without the stores 0.17,
+// Measured (tools/upbox_bench.py, tools/attic/upbox_ablation.py; 32 chunks): 0.315 -> 0.25 ms alone.  Without the voxel loads 0.17, without the stores 0.17,
 // with neither 0.09: a box's loads and stores go out in two bursts and only two workgroups per CU interleave them.  A rotated loop whose waits for
 // the voxels leave the stores in flight (vmcnt(4) instead of vmcnt(0)) and a two-boxes-deep request measured 0.259 / 0.268: not kept.
 namespace {
@@ -1400,16 +1375,7 @@ __global__ __launch_bounds__(512, 4) void k_conv3_up_split_boxp(UpSplitArgs a, i
             }
         if (b + bs < b1 && ((b + bs) >> (3 * lt)) != (b >> (3 * lt))) refresh((b + bs) >> (3 * lt));   // the next box is in another sample (the table was last read before B(b - 1))
         __syncthreads();                                           // A: tile(b - 1) drained by every wave, image(cur ^ 1) free since MFMA(b - 1)
-        {
-            const int col = lane & 15, yj = lane >> 4;
-#pragma unroll
-            for (int m = 0; m < 4; ++m)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int lin = (2 * m + pz) * 64 + (2 * yj + py) * 8 + 2 * r + px;
-                    e[col * UB_E_STRIDE + lin] = rf_relu(rf_split_join(hi[m][0][r], lo[m][0][r]));
-                }
-        }
+        us_acc_to_tile<1, UB_E_STRIDE>(e, hi, lo, lane, pz, py, px);
         if (b + bs < b1) stage(cur ^ 1);
         __syncthreads();                                           // B: tile(b) and image(b + 1) complete
         if (b + 2 * bs < b1) request(b + 2 * bs);
@@ -1430,20 +1396,8 @@ __global__ __launch_bounds__(512, 4) void k_conv3_up_split_boxp(UpSplitArgs a, i
         }
         if (a.stats) {
             const int co = tid >> 3, part = tid & 7;
-            double sm = 0.0, sq = 0.0;
-            if (co < cout) {
-#pragma unroll 4
-                for (int i = 0; i < 16; ++i) {
-                    const float4 v = *reinterpret_cast<const float4*>(e + co * UB_E_STRIDE + (part * 16 + i) * 4);
-                    sm += (double)v.x; sq += (double)v.x * v.x;
-                    sm += (double)v.y; sq += (double)v.y * v.y;
-                    sm += (double)v.z; sq += (double)v.z * v.z;
-                    sm += (double)v.w; sq += (double)v.w * v.w;
-                }
-            }
-#pragma unroll
-            for (int msk = 1; msk < 8; msk <<= 1) { sm += __shfl_xor(sm, msk, 64); sq += __shfl_xor(sq, msk, 64); }
-            if (part == 0 && co < cout) a.stats[((size_t)n * cout + co) * (size_t)(1 << (3 * lt)) + tile] = make_double2(sm, sq);
+            const double2 s = us_box_channel_sums(e, co, part, co < cout);
+            if (part == 0 && co < cout) a.stats[((size_t)n * cout + co) * (size_t)(1 << (3 * lt)) + tile] = s;
         }
     }
 }
@@ -1467,38 +1421,14 @@ __global__ __launch_bounds__(512, 2) void k_conv3_up_split_boxskip(UpSplitArgs a
     const int c0 = a.c0, c1 = a.c1, cin = c0 + c1, nA = c0 >> 3, nB = c1 >> 3, half = edge >> 1, tpe = edge >> 3;
     const int nbt = (a.cout + 15) >> 4;                            // n-blocks of the weight image
     const int nb0 = blockIdx.y * NB;                                // this workgroup's first n-block
-    const unsigned g_ = gridDim.x, per = g_ >> 3, rem = g_ & 7u, kx = blockIdx.x & 7u;
-    int t = (int)(kx * per + (kx < rem ? kx : rem) + (blockIdx.x >> 3));
-    const int tile = t % (tpe * tpe * tpe);
-    const int x0 = (t % tpe) * 8; t /= tpe;
-    const int y0 = (t % tpe) * 8; t /= tpe;
-    const int z0 = (t % tpe) * 8; t /= tpe;
-    const int n = t;
+    const auto [n, tile, z0, y0, x0] = us_box_decode(tpe);
     const float4* __restrict__ aff = a.affine + (size_t)n * cin;
-    const size_t vol = (size_t)edge * edge * edge, hvol = (size_t)half * half * half;
+    const size_t vol = (size_t)edge * edge * edge;
 
     // ---- zero the chunk image's stride padding once (slots the staging never writes are never read either, but keep them defined)
     for (int i = tid; i < US_A_BUF / 16; i += 512) reinterpret_cast<uint4*>(lds + UK_A_OFF)[i] = make_uint4(0u, 0u, 0u, 0u);
 
-    // ---- low-res groups: thread = (channel group, halo voxel); 216 voxels per group
-    for (int u = tid; u < nB * US_BSLOTS; u += 512) {
-        const int cg = u / US_BSLOTS, v = u % US_BSLOTS;
-        const int hz = v / US_BZ, hy = (v / US_BY) % 6, hx = v % 6;
-        const int z = (z0 >> 1) + hz - 1, y = (y0 >> 1) + hy - 1, x = (x0 >> 1) + hx - 1;
-        const bool in = (unsigned)z < (unsigned)half && (unsigned)y < (unsigned)half && (unsigned)x < (unsigned)half;
-        float yv[8];
-        const float* __restrict__ sp = a.src1 + ((size_t)n * c1 + cg * 8) * hvol + (in ? ((size_t)z * half + y) * half + x : 0);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const float4 af = aff[c0 + cg * 8 + j];
-            yv[j] = in ? fmaf(sp[(size_t)j * hvol] - af.x, af.y, af.z) : 0.f;
-        }
-        h8 h, l;
-        rf_split8(yv, h, l);
-        unsigned char* p = lds + UK_B_OFF + cg * 2 * US_B_PLANE + v * 16;
-        *reinterpret_cast<h8*>(p) = h;
-        *reinterpret_cast<h8*>(p + US_B_PLANE) = l;
-    }
+    us_stage_lowres(lds + UK_B_OFF, a.src1, aff + c0, n, c1, nB, half, z0, y0, x0, tid);
 
     // ---- phase-A staging: thread owns halo voxels tid and tid + 512 (the second only below 1000) of the 10^3 box
     int voff[2], vsl[2];
@@ -1610,45 +1540,17 @@ __global__ __launch_bounds__(512, 2) void k_conv3_up_split_boxskip(UpSplitArgs a
 
     // ---- epilogue: relu(hi + lo / 2^11) -> LDS tile [couts of this group][z][y][x] of the box -> float4 half rows, statistics of the box per cout
     float* e = reinterpret_cast<float*>(lds);
-    {
-        const int col = lane & 15, yj = lane >> 4;
-#pragma unroll
-        for (int m = 0; m < 4; ++m)
-#pragma unroll
-            for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int lin = (2 * m + pz) * 64 + (2 * yj + py) * 8 + 2 * r + px;
-                    e[(nb * 16 + col) * UB_E_STRIDE + lin] = rf_relu(rf_split_join(hi[m][nb][r], lo[m][nb][r]));
-                }
-    }
+    us_acc_to_tile<NB, UB_E_STRIDE>(e, hi, lo, lane, pz, py, px);
     __syncthreads();
     const int cob = nb0 * 16;
     int rows = a.cout - cob;
     if (rows > NB * 16) rows = NB * 16;
-    float* __restrict__ o = a.out + ((size_t)n * a.cout + cob) * vol + ((size_t)z0 * edge + y0) * edge + x0;
-    for (int q = tid; q < rows * 128; q += 512) {
-        const int co = q >> 7, l4 = q & 127;
-        const int z = l4 >> 4, y = (l4 >> 1) & 7, xh = l4 & 1;
-        *reinterpret_cast<float4*>(o + (size_t)co * vol + ((size_t)z * edge + y) * edge + xh * 4) = *reinterpret_cast<const float4*>(e + co * UB_E_STRIDE + l4 * 4);
-    }
+    us_store_box_rows(a.out + ((size_t)n * a.cout + cob) * vol + ((size_t)z0 * edge + y0) * edge + x0, e, rows, vol, edge, tid);
     if (a.stats) {
         const int tiles = tpe * tpe * tpe;
         const int co = tid >> 3, part = tid & 7;
-        double sm = 0.0, sq = 0.0;
-        if (co < rows) {
-#pragma unroll 4
-            for (int i = 0; i < 16; ++i) {
-                const float4 v = *reinterpret_cast<const float4*>(e + co * UB_E_STRIDE + (part * 16 + i) * 4);
-                sm += (double)v.x; sq += (double)v.x * v.x;
-                sm += (double)v.y; sq += (double)v.y * v.y;
-                sm += (double)v.z; sq += (double)v.z * v.z;
-                sm += (double)v.w; sq += (double)v.w * v.w;
-            }
-        }
-#pragma unroll
-        for (int msk = 1; msk < 8; msk <<= 1) { sm += __shfl_xor(sm, msk, 64); sq += __shfl_xor(sq, msk, 64); }
-        if (part == 0 && co < rows) a.stats[((size_t)n * a.cout + cob + co) * tiles + tile] = make_double2(sm, sq);
+        const double2 s = us_box_channel_sums(e, co, part, co < rows);
+        if (part == 0 && co < rows) a.stats[((size_t)n * a.cout + cob + co) * tiles + tile] = s;
     }
 }
 
@@ -1679,12 +1581,50 @@ extern "C" int rf_conv3d_up_split_supported(int c0, int c1, int n, int edge, int
     return nb == 3 || nb == 4;
 }
 
+// what every entry point fills in the same way; the output form (out_ch8, pre_out + the next layer's GroupNorm, pre_pm) is off
+static UpSplitArgs up_split_args(const float* src0, int c0, const float* src1, int c1, int n, const float* gn_affine, const void* w_packed, int cout, float* out,
+                                 double* stats) {
+    UpSplitArgs a;
+    a.src0 = src0; a.src1 = src1; a.affine = reinterpret_cast<const float4*>(gn_affine); a.wp = reinterpret_cast<const h8*>(w_packed);
+    a.out = out; a.stats = reinterpret_cast<double2*>(stats); a.c0 = c0; a.c1 = c1; a.n = n; a.cout = cout;
+    a.pre_out = nullptr; a.ngamma = a.nbeta = nullptr; a.ngroups = 0; a.neps = 0.f; a.out_ch8 = 0; a.pre_pm = 0;
+    return a;
+}
+// ... and its pre-split form
+static UpSplitArgs up_split_pre_args(UpSplitArgs a, void* out_presplit, const float* next_gamma, const float* next_beta, int next_groups, float eps, int pre_pm) {
+    a.pre_out = reinterpret_cast<h8*>(out_presplit); a.ngamma = next_gamma; a.nbeta = next_beta; a.ngroups = next_groups; a.neps = eps; a.pre_pm = pre_pm;
+    return a;
+}
+
 template <int NB>
 static int launch_up_split(const UpSplitArgs& a, hipStream_t stream) {
     auto kern = k_conv3_up_split<NB>;
     static RfLdsOptIn opt_in;
     if (int rc = opt_in.ensure(reinterpret_cast<const void*>(kern), US_LDS_ALLOC, "rf_conv3d_up_split_k3_gn_relu")) return rc;
     hipLaunchKernelGGL(kern, dim3((unsigned)a.n), dim3(512), US_LDS_ALLOC, stream, a);
+    RF_CHECK_LAUNCH("rf_conv3d_up_split_k3_gn_relu");
+    return RF_OK;
+}
+
+// the persistent box form: two workgroups per CU (rf_persistent_wgs), each a run of boxes
+template <int NBG, int CGO>
+static int launch_up_split_boxp(const UpSplitArgs& a, int edge, int boxes, hipStream_t stream) {
+    auto kern = k_conv3_up_split_boxp<NBG, CGO>;
+    static RfLdsOptIn opt_in;
+    if (int rc = opt_in.ensure(reinterpret_cast<const void*>(kern), UP_LDS_BYTES, "rf_conv3d_up_split_k3_gn_relu_ch8")) return rc;
+    hipLaunchKernelGGL(kern, dim3((unsigned)rf_persistent_wgs()), dim3(512), UP_LDS_BYTES, stream, a, edge, boxes);
+    RF_CHECK_LAUNCH("rf_conv3d_up_split_k3_gn_relu");
+    return RF_OK;
+}
+
+// boxes with a skip source: NB of the weight image's nbt n-blocks per workgroup; LDS = the larger of the epilogue tile and the images (`img` bytes)
+template <int NB>
+static int launch_up_split_boxskip(const UpSplitArgs& a, int edge, unsigned boxes, int nbt, size_t img, hipStream_t stream) {
+    auto kern = k_conv3_up_split_boxskip<NB>;
+    static RfLdsOptIn opt_in;
+    const size_t tile = (size_t)(NB * 16) * UB_E_STRIDE * 4;
+    if (int rc = opt_in.ensure(reinterpret_cast<const void*>(kern), 160 * 1024, "rf_conv3d_up_split_k3_gn_relu")) return rc;
+    hipLaunchKernelGGL(kern, dim3(boxes, (unsigned)((nbt + NB - 1) / NB)), dim3(512), tile > img ? tile : img, stream, a, edge);
     RF_CHECK_LAUNCH("rf_conv3d_up_split_k3_gn_relu");
     return RF_OK;
 }
@@ -1715,10 +1655,7 @@ extern "C" int rf_conv3d_up_split_k3_gn_relu(const float* src0, int c0, const fl
                "rf_conv3d_up_split_k3_gn_relu: takes whole 8^3 samples (n >= 256, c1 <= 64, 33..64 couts), 4^3 samples (n >= 1024) or 8^3 boxes of edge >= 16 volumes (without a skip source: c1 <= 64, <= 32 couts, >= 256 boxes; with one: c1 <= 96, <= 96 couts, >= 512 boxes); c0 and c1 in multiples of 8 (got c0=%d c1=%d n=%d edge=%d cout=%d)",
                c0, c1, n, edge, cout);
     RF_REQUIRE((c0 == 0 || src0) && src1 && gn_affine && w_packed && out, RF_E_INVALID, "rf_conv3d_up_split_k3_gn_relu: null pointer");
-    UpSplitArgs a;
-    a.src0 = src0; a.src1 = src1; a.affine = reinterpret_cast<const float4*>(gn_affine); a.wp = reinterpret_cast<const h8*>(w_packed);
-    a.out = out; a.stats = reinterpret_cast<double2*>(stats); a.c0 = c0; a.c1 = c1; a.n = n; a.cout = cout;
-    a.pre_out = nullptr; a.ngamma = a.nbeta = nullptr; a.ngroups = 0; a.neps = 0.f; a.out_ch8 = 0; a.pre_pm = 0;
+    UpSplitArgs a = up_split_args(src0, c0, src1, c1, n, gn_affine, w_packed, cout, out, stats);
     return up_split_dispatch(a, c0, c1, n, edge, cout, stream);
 }
 
@@ -1728,18 +1665,11 @@ static int up_split_dispatch(UpSplitArgs& a, int c0, int c1, int n, int edge, in
         const int nbq = rf_round_up(cout, 16) / 16;
         const size_t lds_bytes = (size_t)(nbq * 16) * UB_E_STRIDE * 4 > (size_t)(c1 / 8) * 2 * US_B_PLANE ? (size_t)(nbq * 16) * UB_E_STRIDE * 4 : (size_t)(c1 / 8) * 2 * US_B_PLANE;
         if (a.out_ch8 && (c1 == 8 || c1 == 16) && (cout == 8 || cout == 16) && boxes >= 2048 && (long long)cout * edge * edge * edge < (1ll << 28)) {
-            // persistent form (channel-interleaved output only): two workgroups per CU, each a run of consecutive boxes
-            static RfLdsOptIn opt_p[4];
-#define RF_BOXP(I_, NBG_, CGO_)                                                                                                      \
-            do {                                                                                                                     \
-                if (int rc = opt_p[I_].ensure(reinterpret_cast<const void*>(k_conv3_up_split_boxp<NBG_, CGO_>), UP_LDS_BYTES, "rf_conv3d_up_split_k3_gn_relu_ch8")) return rc; \
-                hipLaunchKernelGGL((k_conv3_up_split_boxp<NBG_, CGO_>), dim3((unsigned)rf_persistent_wgs()), dim3(512), UP_LDS_BYTES, (hipStream_t)stream, a, edge, (int)boxes); \
-            } while (0)
-            if (c1 == 16 && cout == 16) RF_BOXP(0, 2, 2);
-            else if (c1 == 16) RF_BOXP(1, 2, 1);
-            else if (cout == 16) RF_BOXP(2, 1, 2);
-            else RF_BOXP(3, 1, 1);
-#undef RF_BOXP
+            // persistent form (channel-interleaved output only)
+            if (c1 == 16 && cout == 16) return launch_up_split_boxp<2, 2>(a, edge, (int)boxes, (hipStream_t)stream);
+            if (c1 == 16) return launch_up_split_boxp<2, 1>(a, edge, (int)boxes, (hipStream_t)stream);
+            if (cout == 16) return launch_up_split_boxp<1, 2>(a, edge, (int)boxes, (hipStream_t)stream);
+            return launch_up_split_boxp<1, 1>(a, edge, (int)boxes, (hipStream_t)stream);
         } else if (nbq == 1) {
             hipLaunchKernelGGL(k_conv3_up_split_box<1>, dim3(boxes), dim3(512), lds_bytes, (hipStream_t)stream, a, edge);
         } else {
@@ -1754,20 +1684,9 @@ static int up_split_dispatch(UpSplitArgs& a, int c0, int c1, int n, int edge, in
         const unsigned boxes = (unsigned)n * (edge / 8) * (edge / 8) * (edge / 8);
         const int nbt = rf_round_up(cout, 16) / 16;
         const size_t img = (size_t)US_A_BUF + (size_t)(c1 / 8) * 2 * US_B_PLANE;
-        static RfLdsOptIn opt3, opt2, opt1;
-#define RF_BOXSKIP(NB_, OPT_)                                                                                                        \
-        do {                                                                                                                         \
-            const size_t tile = (size_t)(NB_ * 16) * UB_E_STRIDE * 4;                                                                \
-            const size_t lds_bytes = tile > img ? tile : img;                                                                        \
-            if (int rc = OPT_.ensure(reinterpret_cast<const void*>(k_conv3_up_split_boxskip<NB_>), 160 * 1024, "rf_conv3d_up_split_k3_gn_relu")) return rc; \
-            hipLaunchKernelGGL(k_conv3_up_split_boxskip<NB_>, dim3(boxes, (unsigned)((nbt + NB_ - 1) / NB_)), dim3(512), lds_bytes, (hipStream_t)stream, a, edge); \
-        } while (0)
-        if (nbt == 1) RF_BOXSKIP(1, opt1);
-        else if (nbt == 2 || nbt == 4) RF_BOXSKIP(2, opt2);
-        else RF_BOXSKIP(3, opt3);
-#undef RF_BOXSKIP
-        RF_CHECK_LAUNCH("rf_conv3d_up_split_k3_gn_relu");
-        return RF_OK;
+        if (nbt == 1) return launch_up_split_boxskip<1>(a, edge, boxes, nbt, img, (hipStream_t)stream);
+        if (nbt == 2 || nbt == 4) return launch_up_split_boxskip<2>(a, edge, boxes, nbt, img, (hipStream_t)stream);
+        return launch_up_split_boxskip<3>(a, edge, boxes, nbt, img, (hipStream_t)stream);
     }
     if (edge == 4) {
         const int nbt = rf_round_up(cout, 16) / 16;
@@ -1813,10 +1732,8 @@ extern "C" int rf_conv3d_up_split_presplit(const float* src0, int c0, const floa
                "rf_conv3d_up_split_presplit: takes whole 8^3 samples (the shapes rf_conv3d_up_split_supported takes at edge 8) with cout in eights and in whole groups (got c0=%d c1=%d n=%d edge=%d cout=%d groups=%d)",
                c0, c1, n, edge, cout, next_groups);
     RF_REQUIRE((c0 == 0 || src0) && src1 && gn_affine && w_packed && out_presplit && next_gamma && next_beta, RF_E_INVALID, "rf_conv3d_up_split_presplit: null pointer");
-    UpSplitArgs a;
-    a.src0 = src0; a.src1 = src1; a.affine = reinterpret_cast<const float4*>(gn_affine); a.wp = reinterpret_cast<const h8*>(w_packed);
-    a.out = nullptr; a.stats = reinterpret_cast<double2*>(stats); a.c0 = c0; a.c1 = c1; a.n = n; a.cout = cout;
-    a.pre_out = reinterpret_cast<h8*>(out_presplit); a.ngamma = next_gamma; a.nbeta = next_beta; a.ngroups = next_groups; a.neps = eps; a.out_ch8 = 0; a.pre_pm = 0;
+    const UpSplitArgs a = up_split_pre_args(up_split_args(src0, c0, src1, c1, n, gn_affine, w_packed, cout, nullptr, stats), out_presplit, next_gamma, next_beta,
+                                            next_groups, eps, 0);
     if (up_split_pp_takes(c0, c1, n, cout)) return launch_up_split_pp(a, (hipStream_t)stream);
     return rf_round_up(cout, 16) == 48 ? launch_up_split<3>(a, (hipStream_t)stream) : launch_up_split<4>(a, (hipStream_t)stream);
 }
@@ -1835,10 +1752,8 @@ extern "C" int rf_conv3d_up_split_presplit_pm(const float* src0, int c0, const f
                "rf_conv3d_up_split_presplit_pm: takes whole 8^3 samples (n >= 1024), 49..64 couts in eights and in whole groups, c0 >= 32 in sixteens, c1 <= 64 in eights (got c0=%d c1=%d n=%d edge=%d cout=%d groups=%d)",
                c0, c1, n, edge, cout, next_groups);
     RF_REQUIRE(src0 && src1 && gn_affine && w_packed && out_presplit_pm && next_gamma && next_beta, RF_E_INVALID, "rf_conv3d_up_split_presplit_pm: null pointer");
-    UpSplitArgs a;
-    a.src0 = src0; a.src1 = src1; a.affine = reinterpret_cast<const float4*>(gn_affine); a.wp = reinterpret_cast<const h8*>(w_packed);
-    a.out = nullptr; a.stats = reinterpret_cast<double2*>(stats); a.c0 = c0; a.c1 = c1; a.n = n; a.cout = cout;
-    a.pre_out = reinterpret_cast<h8*>(out_presplit_pm); a.ngamma = next_gamma; a.nbeta = next_beta; a.ngroups = next_groups; a.neps = eps; a.out_ch8 = 0; a.pre_pm = 1;
+    const UpSplitArgs a = up_split_pre_args(up_split_args(src0, c0, src1, c1, n, gn_affine, w_packed, cout, nullptr, stats), out_presplit_pm, next_gamma, next_beta,
+                                            next_groups, eps, 1);
     return launch_up_split_pp(a, (hipStream_t)stream);
 }
 
@@ -1857,9 +1772,7 @@ extern "C" int rf_conv3d_up_split_k3_gn_relu_ch8(const float* src0, int c0, cons
                "rf_conv3d_up_split_k3_gn_relu_ch8: takes the box form of rf_conv3d_up_split_k3_gn_relu (no skip source, >= 256 boxes) with cout in eights (got c0=%d c1=%d n=%d edge=%d cout=%d)",
                c0, c1, n, edge, cout);
     RF_REQUIRE(src1 && gn_affine && w_packed && out_ch8, RF_E_INVALID, "rf_conv3d_up_split_k3_gn_relu_ch8: null pointer");
-    UpSplitArgs a;
-    a.src0 = src0; a.src1 = src1; a.affine = reinterpret_cast<const float4*>(gn_affine); a.wp = reinterpret_cast<const h8*>(w_packed);
-    a.out = out_ch8; a.stats = reinterpret_cast<double2*>(stats); a.c0 = c0; a.c1 = c1; a.n = n; a.cout = cout;
-    a.pre_out = nullptr; a.ngamma = a.nbeta = nullptr; a.ngroups = 0; a.neps = 0.f; a.out_ch8 = 1; a.pre_pm = 0;
+    UpSplitArgs a = up_split_args(src0, c0, src1, c1, n, gn_affine, w_packed, cout, out_ch8, stats);
+    a.out_ch8 = 1;
     return up_split_dispatch(a, c0, c1, n, edge, cout, stream);
 }

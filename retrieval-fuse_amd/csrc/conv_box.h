@@ -1,5 +1,5 @@
 // Shared by the box-tiled 3x3x3 convolution kernels (conv3d_mfma.hip: fp32 MFMA; conv3d_split.hip: split-operand F16 MFMA): launch
-// arguments, the voxel order of a wave's accumulator tiles, the XCD-contiguous workgroup order and the EPILOGUE (ReLU + float4 stores,
+// arguments, the voxel order of a wave's accumulator tiles and the EPILOGUE (ReLU + float4 stores,
 // GroupNorm statistics of the output, fused MaxPool3d(2) + its statistics).  Both MFMA families deliver a 16x16 tile with the same
 // lane map (col = lane & 15, rows 4*(lane >> 4) + r), so one epilogue serves both and their outputs / statistics have one layout.
 #pragma once
@@ -42,14 +42,6 @@ struct BoxOrder {
         }
     }
 };
-
-// Workgroups are handed to the 8 XCDs round-robin by linear id, each XCD with its own L2.  Tiles that split a sample
-// (8-voxel = 32-byte row pieces of 64..512-byte rows) would then share every cache line across XCDs: partial-line writes
-// that no L2 can merge and 128-byte fills for 32 bytes of use.  Remap so that XCD k walks a contiguous range of tiles.
-__device__ __forceinline__ unsigned rf_xcd_contiguous(unsigned b, unsigned g) {
-    const unsigned per = g >> 3, rem = g & 7u, k = b & 7u;
-    return k * per + (k < rem ? k : rem) + (b >> 3);
-}
 
 // 512-voxel workgroup tiles (8^3 boxes) when that still gives the 256 CUs a few workgroups each; otherwise the fp32 kernel's 128-voxel tiles
 static inline bool rf_conv_use_big(int n, int edge, int cout16) {

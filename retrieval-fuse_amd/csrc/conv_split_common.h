@@ -1,5 +1,5 @@
-// Shared by the split-operand box kernels (conv3d_split.hip, conv3d_split_zc.hip): the halo-box image in LDS and the pre-split output.  The operand
-// format itself is split_operand.h.
+// Shared by the split-operand kernels (conv3d_split.hip, conv3d_split_zc.hip, conv3d_up_split.hip): the halo-box image in LDS, the pre-split output and
+// the HAND-OVER EPILOGUE that writes it.  The operand format itself is split_operand.h; the triple from (sum, sum of squares) is rf_gn_triple (common.h).
 #pragma once
 #include "common.h"
 #include "split_operand.h"
@@ -32,3 +32,51 @@ struct SplitPreOut {
     const float* pw_b;
     float post_add, post_mul;
 };
+
+// ------------------------------------------------------------------------------------------------------- the hand-over epilogue
+// ReLU'd tile [cout][8^3] in LDS -> per-channel float64 sums -> the next layer's GroupNorm triples -> normalise, split, [h | l] slots.  Three pieces that a
+// kernel composes; its barriers (__syncthreads / lds_barrier) and its opaque copy of the thread index stay with the kernel.
+
+// (sum, sum of squares) of one cout's 512 tile values: TPC threads per cout (`part` = 0 .. TPC - 1) read TPC-strided values, then a butterfly over the TPC
+// lanes -- a fixed order, so every route gives the same bits.  Valid in every lane of the TPC; !live: zeros (the lanes still take part in the butterfly)
+template <int STRIDE, int TPC>
+__device__ __forceinline__ double2 rf_tile_channel_sums(const float* e, int co, int part, bool live) {
+    constexpr int PER = 512 / TPC, UNROLL = PER <= 16 ? PER : 8;
+    double sm = 0.0, sq = 0.0;
+    if (live) {
+#pragma unroll UNROLL
+        for (int i = 0; i < PER; ++i) {
+            const float v = e[co * STRIDE + part + TPC * i];
+            sm += (double)v; sq += (double)v * v;
+        }
+    }
+#pragma unroll
+    for (int msk = 1; msk < TPC; msk <<= 1) { sm += __shfl_xor(sm, msk, 64); sq += __shfl_xor(sq, msk, 64); }
+    return make_double2(sm, sq);
+}
+
+// the next layer's triple of channel c, as rf_gn_from_stats: the sums of its group (cpg channels of `voxels` values each) in channel order, float64
+__device__ __forceinline__ float4 rf_group_triple(const double2* chst, int c, int cpg, double voxels, float eps, const float* gamma, const float* beta) {
+    const int c0 = (c / cpg) * cpg;
+    double sm = 0.0, sq = 0.0;
+    for (int k = c0; k < c0 + cpg; ++k) { sm += chst[k].x; sq += chst[k].y; }
+    return rf_gn_triple(sm, sq, (double)cpg * voxels, (double)eps, gamma[c], beta[c]);
+}
+
+// this thread's voxel of every 8-channel group: value(c) -- a tile read, or the zc kernel's L2 read-back -- normalised by trip[c], split, stored to the h and
+// the l plane (VOX slots each) of group sg; `o` = the sample's pre-split image + this thread's voxel
+template <int VOX, class Value>
+__device__ __forceinline__ void rf_presplit_store(h8* __restrict__ o, int cgroups, const float4* trip, Value&& value) {
+    for (int sg = 0; sg < cgroups; ++sg) {
+        float y[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const float4 t4 = trip[sg * 8 + j];
+            y[j] = fmaf(value(sg * 8 + j) - t4.x, t4.y, t4.z);
+        }
+        h8 h, l;
+        rf_split8(y, h, l);
+        o[(size_t)sg * 2 * VOX] = h;
+        o[(size_t)sg * 2 * VOX + VOX] = l;
+    }
+}

@@ -41,8 +41,8 @@ EPI_OUT = "                if (a.pool_mode != 2) {\n                    if (co_g
 NO_EPI_OUT = "                if (a.pool_mode != 2) {\n                    if (co_g < a.cout && hi[0][0] == 123.456f) {"
 DECL = "    int item = 0;                                                    // parity of the image buffer"
 DECL_STAMP = "    const long long dbg_t0 = __builtin_readcyclecounter();\n    int item = 0;"
-END = "                        o[(size_t)sg * 2 * 512 + 512] = l;\n                    }\n                }\n            }\n        }\n    }\n}"
-END_STAMP = "                        o[(size_t)sg * 2 * 512 + 512] = l;\n                    }\n                }\n            }\n        }\n    }\n    if (lane == 0 && dbg_out) { dbg_out[blockIdx.x * 8 + wave] = (float)(__builtin_readcyclecounter() - dbg_t0); if (wave == 0) { reinterpret_cast<long long*>(dbg_out + 4096)[(blockIdx.y * 512 + blockIdx.x) * 2] = dbg_t0; reinterpret_cast<long long*>(dbg_out + 4096)[(blockIdx.y * 512 + blockIdx.x) * 2 + 1] = __builtin_readcyclecounter(); } }\n}"
+END = "                                           [&](int c) { return e[c * ZM_TILE_STRIDE + tv]; });\n                }\n            }\n        }\n    }\n}"
+END_STAMP = "                                           [&](int c) { return e[c * ZM_TILE_STRIDE + tv]; });\n                }\n            }\n        }\n    }\n    if (lane == 0 && dbg_out) { dbg_out[blockIdx.x * 8 + wave] = (float)(__builtin_readcyclecounter() - dbg_t0); if (wave == 0) { reinterpret_cast<long long*>(dbg_out + 4096)[(blockIdx.y * 512 + blockIdx.x) * 2] = dbg_t0; reinterpret_cast<long long*>(dbg_out + 4096)[(blockIdx.y * 512 + blockIdx.x) * 2 + 1] = __builtin_readcyclecounter(); } }\n}"
 VARIANTS = {'base': [], 'no_mfma': [(MF, NO_MF)], 'no_mid_barrier': [(MID, '')], 'no_loads': [(LOADS_PRE, NO_LOADS_PRE), (LOADS_F32, NO_LOADS_F32)],
             'no_conversion': [(CONV, NO_CONV)], 'no_weight_loads': [(W1, NO_W1), (W0, NO_W0)], 'no_staging': [(LOADS_PRE, NO_LOADS_PRE), (LOADS_F32, NO_LOADS_F32), (SST, NO_SST)],
             'no_epilogue': [(EPI_ALL, NO_EPI_ALL), (EPI_OUT, NO_EPI_OUT)],
