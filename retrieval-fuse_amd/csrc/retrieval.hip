@@ -6,16 +6,20 @@
 // (window cut + normalisation).  FLANN (pyflann, third-party, approximate kd-tree) is NOT restated: the scan below is
 // exact.
 //
-// Scan design (rf_l2_topk)
-//   The DB embedding matrix is stored blocked [block][dim][64 rows] so a wave reads one dim of 64 consecutive rows
-//   with one coalesced 256-byte load.  A wave keeps its 64 rows x 64 dims in 64 VGPRs (one row per lane) and streams
-//   the query tile past them: the query vector comes in through scalar loads (wave-uniform address), each lane
-//   accumulates sum (q_d - x_d)^2 in fp32, compares against the list's current k-th best and only on a hit takes the
-//   (rare) cooperative insertion path.  Candidates are 64-bit keys (dist_bits << 32 | global_row): for non-negative
-//   floats the IEEE bit pattern is monotone, so one unsigned compare orders by (distance, row id) -- ties go to the
-//   lower row id, deterministically.  Every (slice, query) gets one sorted list; a bitonic merge kernel reduces
-//   them per query.  The same merge serves the RCCL all-gathered per-shard lists.
-#include "common.h"
+// Search design (rf_l2_topk)
+//   Candidates are 64-bit keys (dist_bits << 32 | global_row): for non-negative floats the IEEE bit pattern is monotone, so one
+//   unsigned compare orders by (distance, row id) -- ties go to the lower row id, deterministically.  A (query, row) pair has ONE
+//   distance ("THE exact distance" below) whichever scan, slice or shard evaluates it.  Every (slice, query) gets one sorted list.
+//   * k_l2_topk (algo 1): the VALU scan.  The blocked view [block][dim][64 rows] gives a wave one dim of 64 consecutive rows per
+//     coalesced 256-byte load; the wave keeps 64 rows x 64 dims in registers (a row per lane) and streams the queries past them
+//     through scalar loads; every pair is evaluated exactly.  Small shards.
+//   * k_l2_topk_mfma (algo 2) / k_l2_topk_mfma16 (algo 3): the filtered scans.  A matrix-core dot product (fp32 operands / split
+//     f16 operands) discards the pairs that provably cannot enter a list; the rest is re-checked with the exact distance and
+//     offered to the list (topk_offer).  The lists start empty below a per-query bound t0 (topk_prologue).
+//   * k_l2_topk_seed16 + k_merge_wave (seed branch): algo 3's bound t0, from k2 rows chosen by the split filter alone.
+//   * k_merge_wave: a wave per query takes the k2 smallest keys of the slices' lists out of registers.  The same merge serves the
+//     all-gathered per-shard key lists (rf_topk_merge_keys); k_merge_pairs merges (dist, idx) arrays.
+#include "split_operand.h"
 
 typedef unsigned long long u64;
 #define RF_KEY_NONE 0xFFFFFFFFFFFFFFFFull
@@ -135,7 +139,7 @@ extern "C" int rf_gather_windows_split(const void* grid, int n, int c, int g, in
 //   blocked  [ceil(n/64)][64 dims][64 rows]      the VALU scan: one coalesced 256-byte load per dim per wave
 //   rows     [n32][64], n32 = n rounded up to 32   the MFMA scan's A operand: position 16*g + m of a row holds dim 4*m + g, so
 //                                                the 64 contiguous bytes lane (row, g) loads are the dims {4m + g} = the g-th
-//                                                summation chain of the exact distance (see rf_exact_dist below)
+//                                                summation chain of the exact distance ("THE exact distance" at the scans, rf_chain16)
 //   hd       [n32]                               (1 - 2^-15) * |row|^2 / 2, +inf for the padding rows (they never pass the filter)
 //   rows16   [n32][64] f16                       the rows rounded to f16, natural dim order: A operands of the f16-filtered scan (the h pieces)
 //   hd16     [n32]                               (1 - 2^-15) * |row|^2 / 2; -inf for a row with a component beyond the f16 range (always re-checked)
@@ -143,9 +147,32 @@ extern "C" int rf_gather_windows_split(const void* grid, int n, int c, int g, in
 //                                                split operands, so that it is as tight as the fp32-MFMA filter at a fifth of its matrix-pipe cycles)
 #define RF_DIM 64
 #define RF_EPS_FILTER 3.0517578125e-05f            // 2^-15, see the error bound at k_l2_topk_mfma
+constexpr float RF_F16_RANGE = 6.0e4f;             // a row or query with a component at or beyond it stays out of the f16 filter (f16 overflows at 65504)
 
-static inline size_t rf_blocked_floats(int64_t n) { return (size_t)((n + 63) / 64) * RF_DIM * 64; }
-static inline int64_t rf_rows32(int64_t n) { return (n + 31) / 32 * 32; }
+// the views of a packed image built for n_layout rows (the offsets depend on it) and the image's size in floats
+struct DbViews {
+    float *blocked, *rows, *hd, *hd16;
+    _Float16 *rows16, *rows16l;
+    size_t floats;
+};
+static DbViews rf_db_views(float* packed, int64_t n_layout) {
+    const size_t n32 = (size_t)((n_layout + 31) / 32 * 32);
+    const size_t o_rows = (size_t)((n_layout + 63) / 64) * RF_DIM * 64, o_hd = o_rows + n32 * RF_DIM, o_rows16 = o_hd + n32, o_hd16 = o_rows16 + n32 * (RF_DIM / 2),
+                 o_rows16l = o_hd16 + n32;
+    DbViews v = {};
+    v.floats = o_rows16l + n32 * (RF_DIM / 2);
+    if (!packed) return v;                                           // (rf_db_packed_floats asks for the size alone)
+    v.blocked = packed; v.rows = packed + o_rows; v.hd = packed + o_hd; v.hd16 = packed + o_hd16;
+    v.rows16 = reinterpret_cast<_Float16*>(packed + o_rows16); v.rows16l = reinterpret_cast<_Float16*>(packed + o_rows16l);
+    return v;
+}
+
+// the split of split_operand.h without its activation scale and clamp: h = f16(v), l = f16((v - h) * 2^11) (v - h is exact in fp32); |v| < RF_F16_RANGE is the caller's
+__device__ __forceinline__ void rf_split_raw(float v, _Float16& h, _Float16& l) {
+    const _Float16 hh = (_Float16)v;
+    h = hh;
+    l = (_Float16)((v - (float)hh) * SPLIT_LO);
+}
 
 __global__ __launch_bounds__(256) void k_db_pack(const float* __restrict__ emb, long long n, float* __restrict__ blocked, float* __restrict__ rows,
                                                  float* __restrict__ hd, _Float16* __restrict__ rows16, float* __restrict__ hd16, _Float16* __restrict__ rows16l) {
@@ -163,11 +190,8 @@ __global__ __launch_bounds__(256) void k_db_pack(const float* __restrict__ emb, 
         {   // a row with a component beyond the f16 range is all zeros here and has hd16 = -inf: it passes the filter and is re-checked exactly
             bool fits = row < n;
             if (fits)
-                for (int d = 0; d < RF_DIM; ++d) fits = fits && fabsf(emb[(size_t)row * RF_DIM + d]) < 6.0e4f;
-            const float xv = fits ? emb[(size_t)row * RF_DIM + p] : 0.f;
-            const _Float16 xh = (_Float16)xv;
-            rows16[i] = xh;
-            rows16l[i] = (_Float16)((xv - (float)xh) * 2048.f);      // (x - h is exact in fp32)
+                for (int d = 0; d < RF_DIM; ++d) fits = fits && fabsf(emb[(size_t)row * RF_DIM + d]) < RF_F16_RANGE;
+            rf_split_raw(fits ? emb[(size_t)row * RF_DIM + p] : 0.f, rows16[i], rows16l[i]);
         }
     }
     for (long long row = (long long)blockIdx.x * blockDim.x + threadIdx.x; row < n32; row += (long long)gridDim.x * blockDim.x) {
@@ -176,7 +200,7 @@ __global__ __launch_bounds__(256) void k_db_pack(const float* __restrict__ emb, 
             double nd = 0.0, big = 0.0;
             for (int d = 0; d < RF_DIM; ++d) { const double v = emb[(size_t)row * RF_DIM + d]; nd += v * v; big = fmax(big, fabs(v)); }
             h = (float)((1.0 - (double)RF_EPS_FILTER) * 0.5 * nd);
-            h16 = big < 6.0e4 ? (float)((1.0 - (double)RF_EPS_FILTER) * 0.5 * nd) : -INFINITY;
+            h16 = big < (double)RF_F16_RANGE ? (float)((1.0 - (double)RF_EPS_FILTER) * 0.5 * nd) : -INFINITY;
         }
         hd[row] = h;
         hd16[row] = h16;
@@ -185,29 +209,56 @@ __global__ __launch_bounds__(256) void k_db_pack(const float* __restrict__ emb, 
 
 extern "C" size_t rf_db_packed_floats(int64_t n, int dim) {
     (void)dim;
-    return rf_blocked_floats(n) + (size_t)rf_rows32(n) * RF_DIM + (size_t)rf_rows32(n) + (size_t)rf_rows32(n) * (RF_DIM / 2) + (size_t)rf_rows32(n) + (size_t)rf_rows32(n) * (RF_DIM / 2);
+    return rf_db_views(nullptr, n).floats;
 }
 
 extern "C" int rf_db_pack_embeddings(const float* emb, int64_t n, int dim, float* packed, void* stream) {
     RF_REQUIRE(emb && packed && n > 0, RF_E_INVALID, "rf_db_pack_embeddings: bad arguments");
     RF_REQUIRE(dim == RF_DIM, RF_E_UNSUPPORTED, "rf_db_pack_embeddings: embedding dim %d (only 64, the latent_dim of every shipped config)", dim);
-    float* rows = packed + rf_blocked_floats(n);
-    float* hd = rows + (size_t)rf_rows32(n) * RF_DIM;
-    _Float16* rows16 = reinterpret_cast<_Float16*>(hd + rf_rows32(n));
-    float* hd16 = reinterpret_cast<float*>(rows16 + (size_t)rf_rows32(n) * RF_DIM);
-    _Float16* rows16l = reinterpret_cast<_Float16*>(hd16 + rf_rows32(n));
-    const size_t want = (rf_blocked_floats(n) + 255) / 256;
-    hipLaunchKernelGGL(k_db_pack, dim3((unsigned)(want < 8192 ? want : 8192)), dim3(256), 0, (hipStream_t)stream, emb, (long long)n, packed, rows, hd, rows16, hd16, rows16l);
+    const DbViews v = rf_db_views(packed, n);
+    const size_t want = ((size_t)(v.rows - v.blocked) + 255) / 256;     // a thread per float of the blocked view
+    hipLaunchKernelGGL(k_db_pack, dim3((unsigned)(want < 8192 ? want : 8192)), dim3(256), 0, (hipStream_t)stream, emb, (long long)n, v.blocked, v.rows, v.hd, v.rows16, v.hd16, v.rows16l);
     RF_CHECK_LAUNCH("rf_db_pack_embeddings");
     return RF_OK;
 }
 
 // --------------------------------------------------------------------------------------------------- the scans
-// THE exact distance of the path (both scans, every code path): four fp32 FMA chains, chain c over the dims d = 4m + c in
-// the order m = 0..15 with t = q_d - x_d (rounded), acc = fma(t, t, acc) from 0; dist = (c0 + c2) + (c1 + c3).
-// The VALU scan runs the chains as two packed-fp32 accumulators {c0,c1}, {c2,c3} over dim pairs (4m, 4m+1), (4m+2, 4m+3);
-// the MFMA scan's re-check runs chain g on the lane that holds row chunk g.  Same bits everywhere, so a (query, row) pair has
-// ONE distance no matter which scan, slice or shard evaluates it.
+// THE exact distance of the path (every scan, every code path): four fp32 FMA chains, chain c over the dims d = 4m + c in
+// the order m = 0..15 with t = q_d - x_d (rounded), acc = fma(t, t, acc) from 0 (rf_chain16); dist = (c0 + c2) + (c1 + c3)
+// (rf_chain_sum).  The VALU scan runs the chains as two packed-fp32 accumulators {c0,c1}, {c2,c3} over dim pairs (4m, 4m+1),
+// (4m+2, 4m+3); the filtered scans' re-check runs chain g on the lane (r, g) that holds chunk g of row r (rf_dist_lanes), the
+// seed merge runs all four on one lane.  Same bits everywhere, so a (query, row) pair has ONE distance no matter which scan,
+// slice or shard evaluates it.
+__device__ __forceinline__ void rf_load16(float (&v)[16], const float4* p) {       // 64 contiguous bytes = one chain of a chain-ordered row or query
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { const float4 t = p[k]; v[4 * k] = t.x; v[4 * k + 1] = t.y; v[4 * k + 2] = t.z; v[4 * k + 3] = t.w; }
+}
+__device__ __forceinline__ float rf_chain16(const float (&qv)[16], const float (&xv)[16]) {
+    float P = 0.f;
+#pragma unroll
+    for (int m = 0; m < 16; ++m) {
+        const float t = qv[m] - xv[m];
+        P = fmaf(t, t, P);
+    }
+    return P;
+}
+__device__ __forceinline__ float rf_chain16(const float4* qp, const float (&xv)[16]) {
+    float qv[16];
+    rf_load16(qv, qp);
+    return rf_chain16(qv, xv);
+}
+__device__ __forceinline__ float rf_chain16(const float4* qp, const float4* xp) {
+    float xv[16];
+    rf_load16(xv, xp);
+    return rf_chain16(qp, xv);
+}
+__device__ __forceinline__ float rf_chain_sum(float c0, float c1, float c2, float c3) { return (c0 + c2) + (c1 + c3); }
+// lane (r, g) = r + 16 g holds chain g of a row in P: the row's distance, wave-uniform (readlane moves 32-bit patterns)
+__device__ __forceinline__ float rf_dist_lanes(float P, int r) {
+    const unsigned Pb = __float_as_uint(P);
+    return rf_chain_sum(__uint_as_float(__builtin_amdgcn_readlane(Pb, r)), __uint_as_float(__builtin_amdgcn_readlane(Pb, r + 16)),
+                        __uint_as_float(__builtin_amdgcn_readlane(Pb, r + 32)), __uint_as_float(__builtin_amdgcn_readlane(Pb, r + 48)));
+}
 #define RF_TQ 64          // queries per workgroup tile of the VALU scan
 
 // cooperative sorted insert of one wave-uniform candidate into the list held by lanes 0..K2-1 (ascending keys)
@@ -275,7 +326,7 @@ __global__ __launch_bounds__(256) void k_l2_topk(const float* __restrict__ q, in
             const int qi = q0 + j;
             if (qi < nq) {                                           // wave-uniform
                 const float* qp = q + (size_t)qi * RF_DIM;           // wave-uniform address -> scalar loads
-                rf_f32x2 acc01 = {0.f, 0.f}, acc23 = {0.f, 0.f};     // chains {c0, c1} and {c2, c3} (see "THE exact distance")
+                rf_f32x2 acc01 = {0.f, 0.f}, acc23 = {0.f, 0.f};     // chains {c0, c1} and {c2, c3} of THE exact distance (rf_chain16 / rf_chain_sum define it)
 #pragma unroll
                 for (int m = 0; m < RF_DIM / 4; ++m) {
                     const rf_f32x2 qa = {qp[4 * m], qp[4 * m + 1]}, qb = {qp[4 * m + 2], qp[4 * m + 3]};
@@ -330,17 +381,75 @@ __global__ __launch_bounds__(256) void k_l2_topk(const float* __restrict__ q, in
 //   * a passing pair (~k2 * ln(rows per slice / k2) per query and slice) is re-evaluated from the registers that already hold
 //     it: the query chunk comes over by ds_bpermute, chain g runs on lane (r, g), four readlanes combine.  Then the usual
 //     cooperative sorted insert into the wave-private list in LDS and a_q is refreshed.
-//   * the lists start EMPTY with a threshold from a sample pass: rf_l2_topk first runs the VALU scan over the shard's first
-//     rows (n/64, 1 k..16 k of them); T0[q] = the sample's k2-th best exact distance bounds the final k2-th distance from above,
-//     so only pairs with distance <= T0 can matter (the scan covers the sample rows again).  Without it every one of the up to 64
-//     slices would re-discover the threshold: ~k2 ln(rows per slice / k2) re-checks per query and slice instead of
-//     ~k2 * n / sample per query over the whole shard (1 M rows, 2048 queries: 3840 -> 490 re-checks per query).
+//   * the lists start EMPTY below a bound t0[q] >= the final k2-th distance (topk_prologue), so only pairs with distance <= t0 can matter.  Without it
+//     every one of the up to 64 slices would re-discover the threshold: ~k2 ln(rows per slice / k2) re-checks per query and slice instead of
+//     ~k2 * n / (rows behind the bound) per query over the whole shard (1 M rows, 2048 queries, a bound from n/8 rows: 3840 -> 490 re-checks per query).
 // Error bound (why nothing is missed): for fp32 chains of length <= 66 the computed s' differs from the real q.x - hd by at
 // most 66*2^-24 * (sum|q_d x_d| + hd) <= 3.0e-6 (|q|^2+|x|^2); THE exact distance differs from the real |q-x|^2 by at most
 // 66*2^-24 |q-x|^2 <= 7.9e-6 (|q|^2+|x|^2); hd and a_q add rounding of 2^-24.  Real |q-x|^2 = |q|^2 + |x|^2 - 2 q.x, so a pair
 // whose exact distance is below T has  s' >= (|q|^2+|x|^2)(1/2 - 7.0e-6) - T/2 - (1-eps)|x|^2/2 >= a_q  as soon as
 // eps/2 >= 7.0e-6 + 3.0e-6, i.e. eps >= 2.0e-5; eps = 2^-15 = 3.05e-5.  (Rows are visited in ascending id order, so a pair
 // that TIES the list's worst distance can never enter: "<" is enough.)
+
+// ---- the pieces the filtered scans share (a wave = 64 queries x a slice of rows; lists, a_q, h_q and t0 in the wave's own LDS)
+// rows [r_lo, r_hi) of a slice
+__device__ __forceinline__ void slice_rows(int slice, int rows_per_slice, long long n, long long& r_lo, long long& r_hi) {
+    const long long n32 = (n + 31) / 32 * 32;
+    r_lo = (long long)slice * rows_per_slice;                        // multiple of 32
+    r_hi = r_lo + rows_per_slice;
+    if (r_hi > n32) r_hi = n32;
+}
+
+// The lists start EMPTY below a threshold: t0[q] is an upper bound of query q's final k2-th distance (+inf: none), so only pairs with distance <= t0 can matter.
+// algo 3 (F16): the seed's bound (k_l2_topk_seed16 + k_merge_wave).  algo 2: the k2-th best exact distance of rf_l2_topk's nested sample pass over the shard's
+// first rows.  h_q = (1 - eps) |q|^2 / 2, a_q = h_q - t0 / 2; F16: a query with a component beyond the f16 range has h_q = a_q = -inf (everything is re-checked).
+// The caller's wave_barrier + s_waitcnt make the LDS writes visible.
+template <int K2, bool F16>
+__device__ __forceinline__ void topk_prologue(const float* __restrict__ q, int nq, int q0, const float* __restrict__ t0, int t0_stride, u64* lists, float* aqs,
+                                              float* hqs, float* t0s, int lane) {
+    const int qi = q0 + lane;
+    float hq = 0.f, a = INFINITY, t = 0.f;                           // a query that does not exist: nothing passes
+    if (qi < nq) {
+        const float* qp = q + (size_t)qi * RF_DIM;
+        float nqn = 0.f, big = 0.f;
+#pragma unroll
+        for (int d = 0; d < RF_DIM; ++d) { nqn = fmaf(qp[d], qp[d], nqn); big = fmaxf(big, fabsf(qp[d])); }
+        hq = !F16 || big < RF_F16_RANGE ? (1.f - RF_EPS_FILTER) * 0.5f * nqn : -INFINITY;
+        t = t0[(size_t)qi * t0_stride];
+        a = hq - 0.5f * t;                                           // t = +inf (fewer than k2 rows behind the bound): -inf, everything passes
+    }
+    hqs[lane] = hq;
+    aqs[lane] = a;
+    t0s[lane] = t;
+    for (int i = lane; i < 64 * K2; i += 64) lists[i] = RF_KEY_NONE;
+}
+
+// a re-checked pair (wave-uniform) is offered to list ql: it enters if it beats the list's worst entry and the bound; then a_q follows the list
+template <int K2>
+__device__ __forceinline__ void topk_offer(u64* lists, float* aqs, const float* hqs, const float* t0s, int ql, float dist, unsigned global_row, int lane) {
+    const u64 key = make_key(dist, global_row);
+    u64 e = lane < K2 ? lists[ql * K2 + lane] : RF_KEY_NONE;
+    const unsigned wlo = __builtin_amdgcn_readlane((unsigned)(e & 0xffffffffu), K2 - 1);
+    const unsigned whi = __builtin_amdgcn_readlane((unsigned)(e >> 32), K2 - 1);
+    if (key < (((u64)whi << 32) | wlo) && dist <= t0s[ql]) {         // (<=: the row that set the bound must get in)
+        list_insert<K2>(e, lane, key);
+        if (lane < K2) lists[ql * K2 + lane] = e;
+        if (lane == K2 - 1) {                                        // T = min(bound, the list's k2-th distance once it is full)
+            const float tl = e == RF_KEY_NONE ? INFINITY : __uint_as_float((unsigned)(e >> 32));
+            aqs[ql] = hqs[ql] - 0.5f * fminf(tl, t0s[ql]);
+        }
+    }
+}
+
+// parts[slice][q][K2] <- the wave's lists
+template <int K2>
+__device__ __forceinline__ void topk_publish(u64* __restrict__ parts, int slice, int nq, int q0, const u64* lists, int lane) {
+    for (int ql = 0; ql < 64; ++ql) {
+        const int qi = q0 + ql;
+        if (qi < nq && lane < K2) parts[((size_t)slice * nq + qi) * K2 + lane] = lists[ql * K2 + lane];
+    }
+}
+
 template <int K2>
 __global__ __launch_bounds__(256, 2) void k_l2_topk_mfma(const float* __restrict__ q, int nq, const float* __restrict__ rows_img,
                                                          const float* __restrict__ hd, long long n, unsigned row_base, int rows_per_slice,
@@ -352,36 +461,15 @@ __global__ __launch_bounds__(256, 2) void k_l2_topk_mfma(const float* __restrict
     const int slice = blockIdx.x;
     const int q0 = (blockIdx.y * 4 + wave) * 64;                     // this wave's 64 queries
     if (q0 >= nq) return;                                            // no barrier in this kernel: a wave may leave
-    const long long n32 = (n + 31) / 32 * 32;
-    const long long r_lo = (long long)slice * rows_per_slice;        // multiple of 64
-    long long r_hi = r_lo + rows_per_slice;
-    if (r_hi > n32) r_hi = n32;
+    long long r_lo, r_hi;
+    slice_rows(slice, rows_per_slice, n, r_lo, r_hi);
     u64* lists = s_lists[wave];
     float* aqs = s_aq[wave];
     float* hqs = s_hq[wave];
     float* t0s = s_t0[wave];
     const int li = lane & 15, lg = lane >> 4;
 
-    // ---------------------------------------------------------------- lists start empty, thresholds from the sample pass
-    // t0[q] = k2-th best exact distance among the shard's first rows (rf_l2_topk's sample pass, VALU scan): an upper bound of
-    // the final k2-th distance (+inf when the sample holds fewer than k2 rows).
-    for (int ql = lane; ql < 64; ql += 64) {
-        const int qi = q0 + ql;
-        float hq = 0.f, a = INFINITY;                                // a query that does not exist: nothing passes
-        if (qi < nq) {
-            const float* qp = q + (size_t)qi * RF_DIM;
-            float nqn = 0.f;
-#pragma unroll
-            for (int d = 0; d < RF_DIM; ++d) nqn = fmaf(qp[d], qp[d], nqn);
-            hq = (1.f - RF_EPS_FILTER) * 0.5f * nqn;
-            const float t = t0[(size_t)qi * t0_stride];
-            a = hq - 0.5f * t;                                       // t = +inf (sample smaller than k2): -inf, everything passes
-        }
-        hqs[ql] = hq;
-        aqs[ql] = a;
-        t0s[ql] = qi < nq ? t0[(size_t)qi * t0_stride] : 0.f;
-    }
-    for (int i = lane; i < 64 * K2; i += 64) lists[i] = RF_KEY_NONE;
+    topk_prologue<K2, false>(q, nq, q0, t0, t0_stride, lists, aqs, hqs, t0s, lane);
     __builtin_amdgcn_wave_barrier();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 
@@ -400,11 +488,9 @@ __global__ __launch_bounds__(256, 2) void k_l2_topk_mfma(const float* __restrict
     auto load_tile = [&](long long row0, float (&a)[2][16], f32x4 (&h)[2]) {
 #pragma unroll
         for (int mb = 0; mb < 2; ++mb) {
-            const float4* rp = reinterpret_cast<const float4*>(rows_img + (size_t)(row0 + mb * 16 + li) * RF_DIM + 16 * lg);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) { const float4 t = rp[k]; a[mb][4 * k] = t.x; a[mb][4 * k + 1] = t.y; a[mb][4 * k + 2] = t.z; a[mb][4 * k + 3] = t.w; }
+            rf_load16(a[mb], reinterpret_cast<const float4*>(rows_img + (size_t)(row0 + mb * 16 + li) * RF_DIM + 16 * lg));
             const float4 t = *reinterpret_cast<const float4*>(hd + row0 + mb * 16 + 4 * lg);
-            h[mb] = (f32x4){-t.x, -t.y, -t.z, -t.w};
+            h[mb] = (f32x4){-t.x, -t.y, -t.z, -t.w};                  // the accumulators start at -hd of the 4 rows whose D values lane (., lg) holds
         }
     };
 
@@ -456,29 +542,10 @@ __global__ __launch_bounds__(256, 2) void k_l2_topk_mfma(const float* __restrict
                         const long long row = row0 + mb * 16 + r;
                         if (row >= n) continue;
                         // chain g of THE exact distance on lane (r, g): the query chunk comes from lane (n_, g)
-                        float P = 0.f;
+                        float qv[16];
 #pragma unroll
-                        for (int j = 0; j < 16; ++j) {
-                            const float qv = __shfl(b[nb][j], n_ + (lane & 48), 64);
-                            const float t = qv - a[mb][j];
-                            P = fmaf(t, t, P);
-                        }
-                        const unsigned Pb = __float_as_uint(P);        // readlane moves 32-bit patterns
-                        const float c0 = __uint_as_float(__builtin_amdgcn_readlane(Pb, r)), c1 = __uint_as_float(__builtin_amdgcn_readlane(Pb, r + 16));
-                        const float c2 = __uint_as_float(__builtin_amdgcn_readlane(Pb, r + 32)), c3 = __uint_as_float(__builtin_amdgcn_readlane(Pb, r + 48));
-                        const float dist = (c0 + c2) + (c1 + c3);
-                        const u64 key = make_key(dist, row_base + (unsigned)row);
-                        u64 e = lane < K2 ? lists[ql * K2 + lane] : RF_KEY_NONE;
-                        const unsigned wlo = __builtin_amdgcn_readlane((unsigned)(e & 0xffffffffu), K2 - 1);
-                        const unsigned whi = __builtin_amdgcn_readlane((unsigned)(e >> 32), K2 - 1);
-                        if (key < (((u64)whi << 32) | wlo) && dist <= t0s[ql]) {          // (<=: the sample's own k2-th row must get in)
-                            list_insert<K2>(e, lane, key);
-                            if (lane < K2) lists[ql * K2 + lane] = e;
-                            if (lane == K2 - 1) {                    // T = min(sample bound, the list's k2-th distance once it is full)
-                                const float tl = e == RF_KEY_NONE ? INFINITY : __uint_as_float((unsigned)(e >> 32));
-                                aqs[ql] = hqs[ql] - 0.5f * fminf(tl, t0s[ql]);
-                            }
-                        }
+                        for (int j = 0; j < 16; ++j) qv[j] = __shfl(b[nb][j], n_ + (lane & 48), 64);
+                        topk_offer<K2>(lists, aqs, hqs, t0s, ql, rf_dist_lanes(rf_chain16(qv, a[mb]), r), row_base + (unsigned)row, lane);
                     }
                 }
             }
@@ -503,11 +570,7 @@ __global__ __launch_bounds__(256, 2) void k_l2_topk_mfma(const float* __restrict
     }
     __builtin_amdgcn_wave_barrier();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    // publish: parts[slice][q][K2]
-    for (int ql = 0; ql < 64; ++ql) {
-        const int qi = q0 + ql;
-        if (qi < nq && lane < K2) parts[((size_t)slice * nq + qi) * K2 + lane] = lists[ql * K2 + lane];
-    }
+    topk_publish<K2>(parts, slice, nq, q0, lists, lane);
 }
 
 // The same scan with the FILTER on the F16 matrix cores, on SPLIT operands (round 6): x = h + l / 2^11 with h = f16(x), l = f16((x - h) 2^11), rows and queries
@@ -520,14 +583,59 @@ __global__ __launch_bounds__(256, 2) void k_l2_topk_mfma(const float* __restrict
 // a trained encoder pair produces and what bench.py builds since round 6 -- every row of the query's neighbourhood passed such a filter and was re-checked one by
 // one: 2048 queries against 1 M rows 1.1 ms -> 15.4 ms.  Rows or queries with a component beyond the f16 range get hd = -inf / a_q = -inf (always re-checked).
 // Pairs that pass are re-evaluated with THE exact distance from the fp32 rows (fetched for that tile only), so the lists are bit-identical to the other scans'.
-#define RF_EPS_FILTER16 RF_EPS_FILTER              // 2^-15
-typedef _Float16 rf_h8 __attribute__((ext_vector_type(8)));
 // [query][chain g][16] = q[query][4 j + g]: the four summation chains of THE exact distance, contiguous per chain (k_l2_topk_mfma16's re-check reads them)
 __global__ __launch_bounds__(256) void k_query_chains(const float* __restrict__ q, int nq, float* __restrict__ qc) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= (size_t)nq * RF_DIM) return;
     const int p = (int)(i % RF_DIM), g = p >> 4, j = p & 15;
     qc[i] = q[(i / RF_DIM) * RF_DIM + 4 * j + g];
+}
+
+// ---- the pieces of the two split-f16 kernels.  Lane (li, lg) holds k = 32 t + 8 lg + j (t = 0, 1; j = 0..7) of row / query li of a block of 16, as pieces h and l.
+// a tile = 2 m-blocks of 16 rows: their h and l pieces and -hd
+__device__ __forceinline__ void load_tile16(const _Float16* __restrict__ rows16, const _Float16* __restrict__ rows16l, const float* __restrict__ hd, long long row0,
+                                            int li, int lg, h8 (&a16)[2][2], h8 (&a16l)[2][2], f32x4 (&h)[2]) {
+#pragma unroll
+    for (int mb = 0; mb < 2; ++mb) {
+        const h8* rp = reinterpret_cast<const h8*>(rows16 + (size_t)(row0 + mb * 16 + li) * RF_DIM + 8 * lg);
+        a16[mb][0] = rp[0];
+        a16[mb][1] = rp[4];                                           // + 32 halves
+        const h8* rl = reinterpret_cast<const h8*>(rows16l + (size_t)(row0 + mb * 16 + li) * RF_DIM + 8 * lg);
+        a16l[mb][0] = rl[0];
+        a16l[mb][1] = rl[4];
+        const float4 t = *reinterpret_cast<const float4*>(hd + row0 + mb * 16 + 4 * lg);     // (as in k_l2_topk_mfma; through a helper of its own k_l2_topk_mfma16,
+        h[mb] = (f32x4){-t.x, -t.y, -t.z, -t.w};                                             // at the register ceiling, spills 10 VGPRs instead of none)
+    }
+}
+// this lane's 16 dims of query qi (zeros for a query that does not exist)
+__device__ __forceinline__ void load_query16(const float* __restrict__ q, int nq, int qi, int lg, float (&qv)[2][8]) {
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) qv[t][j] = qi < nq ? q[(size_t)qi * RF_DIM + 32 * t + 8 * lg + j] : 0.f;
+}
+// ... as the B operands of n-block nb = 2 np + e, laid out [t][np][e] (rf_split_mfma<2> takes a pair of n-blocks); a query that does not fit f16 becomes zeros
+__device__ __forceinline__ void split_query16(const float (&qv)[2][8], bool fits, h8 (&bh)[2], h8 (&bl)[2]) {
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            _Float16 h, l;
+            rf_split_raw(fits ? qv[t][j] : 0.f, h, l);
+            bh[t][j] = h;
+            bl[t][j] = l;
+        }
+}
+// the split filter product of one m-block against the n-block pair np: s[e][i] = q.x - hd of D row 4 lg + i, query column li of n-block 2 np + e (6 MFMAs per n-block)
+__device__ __forceinline__ void filter_product16(const h8 (&a16)[2], const h8 (&a16l)[2], f32x4 hneg, const h8 (&bq)[2][2][2], const h8 (&bql)[2][2][2], int np,
+                                                 float (&s)[2][4]) {
+    f32x4 hi[2] = {hneg, hneg}, lo[2] = {(f32x4){0.f, 0.f, 0.f, 0.f}, (f32x4){0.f, 0.f, 0.f, 0.f}};
+#pragma unroll
+    for (int t = 0; t < 2; ++t) rf_split_mfma<2>(hi, lo, a16[t], a16l[t], bq[t][np], bql[t][np]);
+#pragma unroll
+    for (int e = 0; e < 2; ++e)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) s[e][i] = rf_split_join(hi[e][i], lo[e][i]);
 }
 
 template <int K2>
@@ -542,117 +650,62 @@ __global__ __launch_bounds__(256, 2) void k_l2_topk_mfma16(const float* __restri
     const int slice = blockIdx.x;
     const int q0 = (blockIdx.y * 4 + wave) * 64;                     // this wave's 64 queries
     if (q0 >= nq) return;                                            // no barrier in this kernel: a wave may leave
-    const long long n32 = (n + 31) / 32 * 32;
-    const long long r_lo = (long long)slice * rows_per_slice;        // multiple of 64
-    long long r_hi = r_lo + rows_per_slice;
-    if (r_hi > n32) r_hi = n32;
+    long long r_lo, r_hi;
+    slice_rows(slice, rows_per_slice, n, r_lo, r_hi);
     u64* lists = s_lists[wave];
     float* aqs = s_aq[wave];
     float* hqs = s_hq[wave];
     float* t0s = s_t0[wave];
     const int li = lane & 15, lg = lane >> 4;
 
-    // ---------------------------------------------------------------- lists start empty, thresholds from the sample pass
-    // t0[q] = k2-th best exact distance among the shard's first rows (rf_l2_topk's sample pass, VALU scan): an upper bound of
-    // the final k2-th distance (+inf when the sample holds fewer than k2 rows).
-    for (int ql = lane; ql < 64; ql += 64) {
-        const int qi = q0 + ql;
-        float hq = 0.f, a = INFINITY;                                // a query that does not exist: nothing passes
-        if (qi < nq) {
-            const float* qp = q + (size_t)qi * RF_DIM;
-            float nqn = 0.f, big = 0.f;
-#pragma unroll
-            for (int d = 0; d < RF_DIM; ++d) { nqn = fmaf(qp[d], qp[d], nqn); big = fmaxf(big, fabsf(qp[d])); }
-            hq = big < 6.0e4f ? (1.f - RF_EPS_FILTER16) * 0.5f * nqn : -INFINITY;     // beyond the f16 range: everything is re-checked
-            const float t = t0[(size_t)qi * t0_stride];
-            a = hq - 0.5f * t;                                       // t = +inf (sample smaller than k2): -inf, everything passes
-        }
-        hqs[ql] = hq;
-        aqs[ql] = a;
-        t0s[ql] = qi < nq ? t0[(size_t)qi * t0_stride] : 0.f;
-    }
-    for (int i = lane; i < 64 * K2; i += 64) lists[i] = RF_KEY_NONE;
+    topk_prologue<K2, true>(q, nq, q0, t0, t0_stride, lists, aqs, hqs, t0s, lane);
     __builtin_amdgcn_wave_barrier();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 
     // ---------------------------------------------------------------- the filtered scan
     // (the fp32 queries are NOT held in registers: the exact re-check reads a query's summation chains from `qc` -- [query][chain g][16] = dims {4 j + g}, written by
     // k_query_chains -- and the 64 registers hold a third tile of rows instead: the scan waits for memory 76 % of its time with one tile requested ahead)
-    rf_h8 bq[4][2], bql[4][2];                                       // the filter's B operands: k = 32 t + 8 lg + j of query q0 + nb*16 + li, as f16 pieces h, l
+    h8 bq[2][2][2], bql[2][2][2];                                    // the filter's B operands (split_query16)
 #pragma unroll
     for (int nb = 0; nb < 4; ++nb) {
-        const int qi = q0 + nb * 16 + li;
+        float qv[2][8];
+        load_query16(q, nq, q0 + nb * 16 + li, lg, qv);
+        h8 bh[2], bl[2];
+        split_query16(qv, hqs[nb * 16 + li] != -INFINITY, bh, bl);   // out-of-range query: zeros, a_q = -inf
 #pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float qv = qi < nq && hqs[nb * 16 + li] != -INFINITY ? q[(size_t)qi * RF_DIM + 32 * t + 8 * lg + j] : 0.f;   // out-of-range query: zeros, a_q = -inf
-                const _Float16 qh = (_Float16)qv;
-                bq[nb][t][j] = qh;
-                bql[nb][t][j] = (_Float16)((qv - (float)qh) * 2048.f);
-            }
+        for (int t = 0; t < 2; ++t) { bq[t][nb >> 1][nb & 1] = bh[t]; bql[t][nb >> 1][nb & 1] = bl[t]; }
     }
     float aq[4];
 #pragma unroll
     for (int nb = 0; nb < 4; ++nb) aq[nb] = aqs[nb * 16 + li];
 
-    auto load_tile = [&](long long row0, rf_h8 (&a16)[2][2], rf_h8 (&a16l)[2][2], f32x4 (&h)[2]) {
-#pragma unroll
-        for (int mb = 0; mb < 2; ++mb) {
-            const rf_h8* rp = reinterpret_cast<const rf_h8*>(rows16 + (size_t)(row0 + mb * 16 + li) * RF_DIM + 8 * lg);
-            a16[mb][0] = rp[0];
-            a16[mb][1] = rp[4];                                       // + 32 halves
-            const rf_h8* rl = reinterpret_cast<const rf_h8*>(rows16l + (size_t)(row0 + mb * 16 + li) * RF_DIM + 8 * lg);
-            a16l[mb][0] = rl[0];
-            a16l[mb][1] = rl[4];
-            const float4 t = *reinterpret_cast<const float4*>(hd + row0 + mb * 16 + 4 * lg);
-            h[mb] = (f32x4){-t.x, -t.y, -t.z, -t.w};
-        }
-    };
-    // the fp32 rows of a tile, fetched only when some pair passed the filter (the exact re-check reads them)
-    auto load_exact = [&](long long row0, float (&a)[2][16]) {
-#pragma unroll
-        for (int mb = 0; mb < 2; ++mb) {
-            const float4* rp = reinterpret_cast<const float4*>(rows_img + (size_t)(row0 + mb * 16 + li) * RF_DIM + 16 * lg);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) { const float4 t = rp[k]; a[mb][4 * k] = t.x; a[mb][4 * k + 1] = t.y; a[mb][4 * k + 2] = t.z; a[mb][4 * k + 3] = t.w; }
-        }
-    };
+    auto load_tile = [&](long long row0, h8 (&a16)[2][2], h8 (&a16l)[2][2], f32x4 (&h)[2]) { load_tile16(rows16, rows16l, hd, row0, li, lg, a16, a16l, h); };
 
-    auto scan_tile = [&](long long row0, const rf_h8 (&a16)[2][2], const rf_h8 (&a16l)[2][2], const f32x4 (&h)[2]) {
-        // the tile in four quarters (m-block x pair of n-blocks): 2 x 2 accumulators live at a time -- the kernel holds the 64 queries three times over
-        // (fp32 for the exact re-check, h and l pieces for the filter) and two tiles of rows
+    auto scan_tile = [&](long long row0, const h8 (&a16)[2][2], const h8 (&a16l)[2][2], const f32x4 (&h)[2]) {
+        // the tile in four quarters (m-block x pair of n-blocks): 2 x 2 accumulators live at a time -- the kernel holds the 64 queries twice over
+        // (h and l pieces for the filter) and three tiles of rows
         unsigned m = 0u;                                              // bit (mb*4 + nb)*4 + i: D row 4*lg + i of m-block mb, query column li of n-block nb
         unsigned long long anyhit = 0ull;
 #pragma unroll
         for (int mb = 0; mb < 2; ++mb)
 #pragma unroll
             for (int np = 0; np < 2; ++np) {
-                f32x4 acc[2], acl[2];
-#pragma unroll
-                for (int e = 0; e < 2; ++e) { acc[e] = h[mb]; acl[e] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
-#pragma unroll
-                for (int t = 0; t < 2; ++t) {
-#pragma unroll
-                    for (int e = 0; e < 2; ++e) acc[e] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a16[mb][t], bq[2 * np + e][t], acc[e], 0, 0, 0);
-#pragma unroll
-                    for (int e = 0; e < 2; ++e) acl[e] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a16[mb][t], bql[2 * np + e][t], acl[e], 0, 0, 0);
-#pragma unroll
-                    for (int e = 0; e < 2; ++e) acl[e] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a16l[mb][t], bq[2 * np + e][t], acl[e], 0, 0, 0);
-                }
+                float sv[2][4];
+                filter_product16(a16[mb], a16l[mb], h[mb], bq, bql, np, sv);
 #pragma unroll
                 for (int e = 0; e < 2; ++e)
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
-                        const bool pass = fmaf(acl[e][i], 1.0f / 2048.f, acc[e][i]) >= aq[2 * np + e];
+                        const bool pass = sv[e][i] >= aq[2 * np + e];
                         anyhit |= __ballot(pass);
                         m |= (pass ? 1u : 0u) << ((mb * 4 + 2 * np + e) * 4 + i);
                     }
             }
         if (anyhit == 0ull) return;
-        // ---- some pair passed the filter: fetch the tile's fp32 rows, exact re-check from registers
+        // ---- some pair passed the filter: fetch the tile's fp32 rows (the exact re-check reads them), exact re-check from registers
         float a[2][16];
-        load_exact(row0, a);
+#pragma unroll
+        for (int mb = 0; mb < 2; ++mb) rf_load16(a[mb], reinterpret_cast<const float4*>(rows_img + (size_t)(row0 + mb * 16 + li) * RF_DIM + 16 * lg));
 #pragma unroll
         for (int mb = 0; mb < 2; ++mb)
 #pragma unroll
@@ -667,17 +720,7 @@ __global__ __launch_bounds__(256, 2) void k_l2_topk_mfma16(const float* __restri
                     int qi = q0 + ql;
                     qi = qi < nq ? qi : nq - 1;
                     // chain g of THE exact distance of query n_ against the m-block's 16 rows, ONCE: lane (r, g) runs chain g of row r
-                    const float4* qp = reinterpret_cast<const float4*>(qc + (size_t)qi * RF_DIM + 16 * lg);
-                    float P = 0.f;
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const float4 qv = qp[k];
-                        float t = qv.x - a[mb][4 * k]; P = fmaf(t, t, P);
-                        t = qv.y - a[mb][4 * k + 1]; P = fmaf(t, t, P);
-                        t = qv.z - a[mb][4 * k + 2]; P = fmaf(t, t, P);
-                        t = qv.w - a[mb][4 * k + 3]; P = fmaf(t, t, P);
-                    }
-                    const unsigned Pb = __float_as_uint(P);            // readlane moves 32-bit patterns
+                    const float P = rf_chain16(reinterpret_cast<const float4*>(qc + (size_t)qi * RF_DIM + 16 * lg), a[mb]);
 #pragma unroll
                     for (int g_ = 0; g_ < 4; ++g_) {
                         unsigned mi = __builtin_amdgcn_readlane(m4, n_ + 16 * g_);
@@ -687,21 +730,7 @@ __global__ __launch_bounds__(256, 2) void k_l2_topk_mfma16(const float* __restri
                             const int r = 4 * g_ + i;                 // row of the m-block
                             const long long row = row0 + mb * 16 + r;
                             if (row >= n) continue;
-                            const float c0 = __uint_as_float(__builtin_amdgcn_readlane(Pb, r)), c1 = __uint_as_float(__builtin_amdgcn_readlane(Pb, r + 16));
-                            const float c2 = __uint_as_float(__builtin_amdgcn_readlane(Pb, r + 32)), c3 = __uint_as_float(__builtin_amdgcn_readlane(Pb, r + 48));
-                            const float dist = (c0 + c2) + (c1 + c3);
-                            const u64 key = make_key(dist, row_base + (unsigned)row);
-                            u64 e = lane < K2 ? lists[ql * K2 + lane] : RF_KEY_NONE;
-                            const unsigned wlo = __builtin_amdgcn_readlane((unsigned)(e & 0xffffffffu), K2 - 1);
-                            const unsigned whi = __builtin_amdgcn_readlane((unsigned)(e >> 32), K2 - 1);
-                            if (key < (((u64)whi << 32) | wlo) && dist <= t0s[ql]) {          // (<=: the sample's own k2-th row must get in)
-                                list_insert<K2>(e, lane, key);
-                                if (lane < K2) lists[ql * K2 + lane] = e;
-                                if (lane == K2 - 1) {                    // T = min(sample bound, the list's k2-th distance once it is full)
-                                    const float tl = e == RF_KEY_NONE ? INFINITY : __uint_as_float((unsigned)(e >> 32));
-                                    aqs[ql] = hqs[ql] - 0.5f * fminf(tl, t0s[ql]);
-                                }
-                            }
+                            topk_offer<K2>(lists, aqs, hqs, t0s, ql, rf_dist_lanes(P, r), row_base + (unsigned)row, lane);
                         }
                     }
                 }
@@ -713,7 +742,7 @@ __global__ __launch_bounds__(256, 2) void k_l2_topk_mfma16(const float* __restri
     };
 
     // three tiles of rows in registers: two requested ahead
-    rf_h8 a0[2][2], a1[2][2], a2[2][2], l0[2][2], l1[2][2], l2[2][2];
+    h8 a0[2][2], a1[2][2], a2[2][2], l0[2][2], l1[2][2], l2[2][2];
     f32x4 h0[2], h1[2], h2[2];
     long long row0 = r_lo;
     if (row0 < r_hi) load_tile(row0, a0, l0, h0);
@@ -733,11 +762,7 @@ __global__ __launch_bounds__(256, 2) void k_l2_topk_mfma16(const float* __restri
     }
     __builtin_amdgcn_wave_barrier();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    // publish: parts[slice][q][K2]
-    for (int ql = 0; ql < 64; ++ql) {
-        const int qi = q0 + ql;
-        if (qi < nq && lane < K2) parts[((size_t)slice * nq + qi) * K2 + lane] = lists[ql * K2 + lane];
-    }
+    topk_publish<K2>(parts, slice, nq, q0, lists, lane);
 }
 
 // The SEED of the filtered scan (round 6; it replaced an exact VALU / nested filtered scan of the shard's first n/8 rows: 0.14 ms of the 0.41 ms search at
@@ -765,37 +790,26 @@ __global__ __launch_bounds__(256, 2) void k_l2_topk_seed16(const float* __restri
     const int slice = blockIdx.x;
     const int q0 = (blockIdx.y * 4 + wave) * 64;
     if (q0 >= nq) return;
-    const long long n32 = (n + 31) / 32 * 32;
-    const long long r_lo = (long long)slice * rows_per_slice;        // multiple of 32
-    long long r_hi = r_lo + rows_per_slice;
-    if (r_hi > n32) r_hi = n32;
+    long long r_lo, r_hi;
+    slice_rows(slice, rows_per_slice, n, r_lo, r_hi);
     const int li = lane & 15, lg = lane >> 4;
 
-    rf_h8 bq[4][2], bql[4][2];
+    h8 bq[2][2][2], bql[2][2][2];
 #pragma unroll
     for (int nb = 0; nb < 4; ++nb) {
-        const int qi = q0 + nb * 16 + li;
         float qv[2][8];
+        load_query16(q, nq, q0 + nb * 16 + li, lg, qv);
         float big = 0.f;
 #pragma unroll
         for (int t = 0; t < 2; ++t)
 #pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                qv[t][j] = qi < nq ? q[(size_t)qi * RF_DIM + 32 * t + 8 * lg + j] : 0.f;
-                big = fmaxf(big, fabsf(qv[t][j]));
-            }
+            for (int j = 0; j < 8; ++j) big = fmaxf(big, fabsf(qv[t][j]));
         big = fmaxf(big, __shfl_xor(big, 16, 64));                    // the query's four lanes hold its 64 dims between them
         big = fmaxf(big, __shfl_xor(big, 32, 64));
-        const bool fits = big < 6.0e4f;                               // beyond the f16 range: zeros (the seed rows of such a query are arbitrary, the bound stays valid)
+        h8 bh[2], bl[2];
+        split_query16(qv, big < RF_F16_RANGE, bh, bl);                // beyond the f16 range: zeros (the seed rows of such a query are arbitrary, the bound stays valid)
 #pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float v = fits ? qv[t][j] : 0.f;
-                const _Float16 qh = (_Float16)v;
-                bq[nb][t][j] = qh;
-                bql[nb][t][j] = (_Float16)((v - (float)qh) * 2048.f);
-            }
+        for (int t = 0; t < 2; ++t) { bq[t][nb >> 1][nb & 1] = bh[t]; bql[t][nb >> 1][nb & 1] = bl[t]; }
     }
     float best[4][4];                                                // slot (n-block, i): rows 16 u + 4 lg + i of the slice, u = 2 tile + m-block
     int bu[4][4];
@@ -804,48 +818,25 @@ __global__ __launch_bounds__(256, 2) void k_l2_topk_seed16(const float* __restri
 #pragma unroll
         for (int i = 0; i < 4; ++i) { best[nb][i] = -INFINITY; bu[nb][i] = -1; }
 
-    auto load_tile = [&](long long row0, rf_h8 (&a16)[2][2], rf_h8 (&a16l)[2][2], f32x4 (&h)[2]) {
-#pragma unroll
-        for (int mb = 0; mb < 2; ++mb) {
-            const rf_h8* rp = reinterpret_cast<const rf_h8*>(rows16 + (size_t)(row0 + mb * 16 + li) * RF_DIM + 8 * lg);
-            a16[mb][0] = rp[0];
-            a16[mb][1] = rp[4];
-            const rf_h8* rl = reinterpret_cast<const rf_h8*>(rows16l + (size_t)(row0 + mb * 16 + li) * RF_DIM + 8 * lg);
-            a16l[mb][0] = rl[0];
-            a16l[mb][1] = rl[4];
-            const float4 t = *reinterpret_cast<const float4*>(hd + row0 + mb * 16 + 4 * lg);
-            h[mb] = (f32x4){-t.x, -t.y, -t.z, -t.w};
-        }
-    };
-    auto scan_tile = [&](int tile, const rf_h8 (&a16)[2][2], const rf_h8 (&a16l)[2][2], const f32x4 (&h)[2]) {
+    auto load_tile = [&](long long row0, h8 (&a16)[2][2], h8 (&a16l)[2][2], f32x4 (&h)[2]) { load_tile16(rows16, rows16l, hd, row0, li, lg, a16, a16l, h); };
+    auto scan_tile = [&](int tile, const h8 (&a16)[2][2], const h8 (&a16l)[2][2], const f32x4 (&h)[2]) {
 #pragma unroll
         for (int mb = 0; mb < 2; ++mb)
 #pragma unroll
             for (int np = 0; np < 2; ++np) {
-                f32x4 acc[2], acl[2];
-#pragma unroll
-                for (int e = 0; e < 2; ++e) { acc[e] = h[mb]; acl[e] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
-#pragma unroll
-                for (int t = 0; t < 2; ++t) {
-#pragma unroll
-                    for (int e = 0; e < 2; ++e) acc[e] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a16[mb][t], bq[2 * np + e][t], acc[e], 0, 0, 0);
-#pragma unroll
-                    for (int e = 0; e < 2; ++e) acl[e] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a16[mb][t], bql[2 * np + e][t], acl[e], 0, 0, 0);
-#pragma unroll
-                    for (int e = 0; e < 2; ++e) acl[e] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a16l[mb][t], bq[2 * np + e][t], acl[e], 0, 0, 0);
-                }
+                float sv[2][4];
+                filter_product16(a16[mb], a16l[mb], h[mb], bq, bql, np, sv);
 #pragma unroll
                 for (int e = 0; e < 2; ++e)
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
-                        const float sv = fmaf(acl[e][i], 1.0f / 2048.f, acc[e][i]);
-                        const bool better = sv > best[2 * np + e][i];
-                        best[2 * np + e][i] = better ? sv : best[2 * np + e][i];
+                        const bool better = sv[e][i] > best[2 * np + e][i];
+                        best[2 * np + e][i] = better ? sv[e][i] : best[2 * np + e][i];
                         bu[2 * np + e][i] = better ? 2 * tile + mb : bu[2 * np + e][i];
                     }
             }
     };
-    rf_h8 a0[2][2], a1[2][2], l0[2][2], l1[2][2];
+    h8 a0[2][2], a1[2][2], l0[2][2], l1[2][2];
     f32x4 h0[2], h1[2];
     long long row0 = r_lo;
     int tile = 0;
@@ -942,21 +933,7 @@ __global__ __launch_bounds__(256) void k_merge_wave(const u64* __restrict__ part
             if (mine != RF_KEY_NONE) {
                 const float4* xp = reinterpret_cast<const float4*>(seed_rows + (size_t)(unsigned)(mine & 0xffffffffu) * RF_DIM);
                 const float4* qp = reinterpret_cast<const float4*>(seed_q + (size_t)qi * RF_DIM);
-                float c[4];
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    float P = 0.f;
-#pragma unroll
-                    for (int kk = 0; kk < 4; ++kk) {
-                        const float4 qv = qp[4 * g + kk], xv = xp[4 * g + kk];
-                        float t = qv.x - xv.x; P = fmaf(t, t, P);
-                        t = qv.y - xv.y; P = fmaf(t, t, P);
-                        t = qv.z - xv.z; P = fmaf(t, t, P);
-                        t = qv.w - xv.w; P = fmaf(t, t, P);
-                    }
-                    c[g] = P;
-                }
-                dist = (c[0] + c[2]) + (c[1] + c[3]);
+                dist = rf_chain_sum(rf_chain16(qp, xp), rf_chain16(qp + 4, xp + 4), rf_chain16(qp + 8, xp + 8), rf_chain16(qp + 12, xp + 12));
             }
         }
         dist = wave_max(dist);
@@ -1011,6 +988,29 @@ static int launch_merge(const u64* parts, int nparts, int nq, int width, int k2,
 // (round 6, split-operand filter, tools/topk_shard_shapes.py: 2048 x 50 k 0.37 / VALU 0.45 ms; 4096 x 25 k 0.41 / 0.43; 8192 x 12.5 k 0.55 / 0.44; 16384 x 125 k 2.9 / 6.1)
 static bool use_mfma_scan(int nq, int64_t n) { return n >= 20000 && (double)nq * (double)n >= 4.0e7; }
 
+// The rows behind the bound t0 of a filtered scan, as a fraction of the shard.  algo 3's seed: n / TOPK_SEED_DIV up to 131072 rows, a quarter of that above
+// (measured, tools/topk_bench.py: 50 k rows n/2 0.19 ms, n/8 0.22; 1 M rows n/8 1.28, n/2 1.53).  algo 2's nested sample pass: n / TOPK_SAMPLE_DIV (round 5: n/64 -> n/8).
+constexpr int TOPK_SEED_DIV = 2, TOPK_SAMPLE_DIV = 8;
+
+// `units` of rows (64-row blocks, 32-row tiles) cut into slices = lists per query to merge: enough for ~target_waves waves over `groups` query groups,
+// at most 64 (the workspace and the merge hold 64 lists per query) and at most `cap` (a floor on the rows per list)
+struct TopkSlices { int count; long long per; };
+static TopkSlices topk_slices(long long units, int groups, int target_waves, long long cap) {
+    long long sl = (target_waves + groups - 1) / groups;
+    if (sl > 64) sl = 64;
+    if (sl > cap) sl = cap;
+    if (sl < 1) sl = 1;
+    const long long per = (units + sl - 1) / sl;
+    return {(int)((units + per - 1) / per), per};
+}
+
+// the <8> / <16> fork of the list width
+#define RF_LAUNCH_K2(kern, k2p, grid, stream, ...)                                                   \
+    do {                                                                                             \
+        if ((k2p) == 8) hipLaunchKernelGGL(kern<8>, grid, dim3(256), 0, stream, __VA_ARGS__);        \
+        else hipLaunchKernelGGL(kern<16>, grid, dim3(256), 0, stream, __VA_ARGS__);                  \
+    } while (0)
+
 // workspace: [per-slice lists: 64 x nq x k2p keys][sample pass: nq x k2p (dist f32, idx i64)]
 // n_layout: the row count the packed image was built for (the offsets of its views depend on it); n <= n_layout: the rows scanned (the first n of the shard)
 static int topk_impl(const float* q, int nq, int dim, const float* db_packed, int64_t n, int64_t n_layout, int64_t row_base, int k2, int algo,
@@ -1025,89 +1025,55 @@ static int topk_impl(const float* q, int nq, int dim, const float* db_packed, in
     const long long nblk = (n + 63) / 64;
     const int k2p = k2 <= 8 ? 8 : 16;
     u64* parts = (u64*)ws;
-    int slices;
+    TopkSlices sl;
     const bool mfma = algo == 2 || algo == 3 || (algo == 0 && use_mfma_scan(nq, n));
     const bool f16_filter = algo != 2;
     if (mfma) {
-        // one wave per (slice, 64 queries); two waves per SIMD on 256 CUs = 2048 waves; at least 128 rows per list, at most 64 lists
+        // one wave per (slice, 64 queries); two waves per SIMD on 256 CUs = 2048 waves; at least 128 rows per list
         const int qgroups = (nq + 63) / 64, qtiles = (qgroups + 3) / 4;
-        long long sl = (2048 + qgroups - 1) / qgroups;
-        if (sl > 64) sl = 64;
-        if (sl > nblk / 2) sl = nblk / 2;
-        if (sl < 1) sl = 1;
-        const long long bps = (nblk + sl - 1) / sl;
-        slices = (int)((nblk + bps - 1) / bps);
-        const float* rows_img = db_packed + rf_blocked_floats(n_layout);
-        const float* hd = rows_img + (size_t)rf_rows32(n_layout) * RF_DIM;
-        // The threshold pass.  fp32-filtered scan (algo 2, kept for comparison): exact top-k2p of the first n/8 rows by this function itself (VALU scan, or
-        // nested filtered scans for big samples); its k2-th distance bounds the final one.  f16-filtered scan: k_l2_topk_seed16 + k_merge_wave (see there) over the
-        // first n / RF_TOPK_SEED_DIV rows.
-#ifndef RF_TOPK_SAMPLE_DIV
-#define RF_TOPK_SAMPLE_DIV 8
-#endif
-#ifndef RF_TOPK_SEED_DIV
-#define RF_TOPK_SEED_DIV 2
-#endif
+        sl = topk_slices(nblk, qgroups, 2048, nblk / 2);
+        const int rows_per_slice = (int)(sl.per * 64);
+        const DbViews v = rf_db_views(const_cast<float*>(db_packed), n_layout);      // (the scans only read)
         float* t_dist = reinterpret_cast<float*>(parts + (size_t)64 * nq * k2p);
         int64_t* t_idx = reinterpret_cast<int64_t*>(t_dist + (size_t)nq * k2p) ;
         float* qc = reinterpret_cast<float*>(t_idx + (size_t)nq * k2p);
-        const _Float16* rows16 = reinterpret_cast<const _Float16*>(hd + rf_rows32(n_layout));
-        const float* hd16 = reinterpret_cast<const float*>(rows16 + (size_t)rf_rows32(n_layout) * RF_DIM);
-        const _Float16* rows16l = reinterpret_cast<const _Float16*>(hd16 + rf_rows32(n_layout));
-        const float* t0;
-        int t0_stride;
         if (f16_filter) {
+            // the bound t0: k_l2_topk_seed16 + k_merge_wave (see there) over the shard's first rows
             hipLaunchKernelGGL(k_query_chains, dim3((unsigned)(((size_t)nq * RF_DIM + 255) / 256)), dim3(256), 0, s, q, nq, qc);
-            long long seed = n / (n <= 131072 ? RF_TOPK_SEED_DIV : 4 * RF_TOPK_SEED_DIV);     // measured (tools/topk_bench.py): 50 k rows n/2 0.19 ms, n/8 0.22; 1 M rows n/8 1.28, n/2 1.53
+            long long seed = n / (n <= 131072 ? TOPK_SEED_DIV : 4 * TOPK_SEED_DIV);
             if (seed < 2048) seed = 2048;
             seed = (seed + 63) / 64 * 64;
             if (seed > n) seed = n;
-            // 8 candidates per (slice, query) in the lists' workspace (64 k2p keys per query): at most 64 slices, at least 8 tiles each, ~2048 waves if possible
+            // 8 candidates per (slice, query) in the lists' workspace (64 k2p keys per query): at least 8 tiles per slice, ~2048 waves if possible
             const long long tiles = (seed + 31) / 32;
-            long long ssl = (2048 + qgroups - 1) / qgroups;
-            if (ssl > 64) ssl = 64;
-            if (ssl > tiles / 8) ssl = tiles / 8;
-            if (ssl < 1) ssl = 1;
-            const long long tps = (tiles + ssl - 1) / ssl;
-            const int sslices = (int)((tiles + tps - 1) / tps);
-            hipLaunchKernelGGL(k_l2_topk_seed16, dim3(sslices, qtiles), dim3(256), 0, s, q, nq, rows16, rows16l, hd16, (long long)seed, (int)(tps * 32), parts);
+            const TopkSlices ss = topk_slices(tiles, qgroups, 2048, tiles / 8);
+            hipLaunchKernelGGL(k_l2_topk_seed16, dim3(ss.count, qtiles), dim3(256), 0, s, q, nq, v.rows16, v.rows16l, v.hd16, (long long)seed, (int)(ss.per * 32), parts);
             RF_CHECK_LAUNCH("rf_l2_topk(seed)");
-            int rc = launch_merge(parts, sslices, nq, 8, k2, nullptr, nullptr, nullptr, s, "rf_l2_topk(seed merge)", qc, rows_img, t_dist);
+            int rc = launch_merge(parts, ss.count, nq, 8, k2, nullptr, nullptr, nullptr, s, "rf_l2_topk(seed merge)", qc, v.rows, t_dist);
             if (rc != RF_OK) return rc;
-            t0 = t_dist;
-            t0_stride = 1;
+            RF_LAUNCH_K2(k_l2_topk_mfma16, k2p, dim3(sl.count, qtiles), s, q, nq, v.rows, v.rows16, v.rows16l, v.hd16, (long long)n, (unsigned)row_base, rows_per_slice, t_dist, 1, parts, qc);
         } else {
-            long long sample = n / RF_TOPK_SAMPLE_DIV;
+            // the bound t0 (algo 2, kept for comparison): exact top-k2p of the first n / TOPK_SAMPLE_DIV rows by this function itself (VALU scan, or nested
+            // filtered scans for big samples); the k2-th best of query qi is t0[qi * k2p]
+            long long sample = n / TOPK_SAMPLE_DIV;
             if (sample < 1024) sample = 1024;
             sample = (sample + 63) / 64 * 64;
             if (sample > n) sample = n;
             const int sample_algo = use_mfma_scan(nq, sample) ? 2 : 1;
             int rc = topk_impl(q, nq, dim, db_packed, sample, n_layout, row_base, k2p, sample_algo, t_dist, t_idx, nullptr, ws, ws_bytes, stream);
             if (rc != RF_OK) return rc;
-            t0 = t_dist + (k2 - 1);                                   // the k2-th best of query qi: t0[qi * k2p]
-            t0_stride = k2p;
+            RF_LAUNCH_K2(k_l2_topk_mfma, k2p, dim3(sl.count, qtiles), s, q, nq, v.rows, v.hd, (long long)n, (unsigned)row_base, rows_per_slice, t_dist + (k2 - 1), k2p, parts);
         }
-        if (f16_filter) {
-            if (k2p == 8) hipLaunchKernelGGL(k_l2_topk_mfma16<8>, dim3(slices, qtiles), dim3(256), 0, s, q, nq, rows_img, rows16, rows16l, hd16, (long long)n, (unsigned)row_base, (int)(bps * 64), t0, t0_stride, parts, qc);
-            else hipLaunchKernelGGL(k_l2_topk_mfma16<16>, dim3(slices, qtiles), dim3(256), 0, s, q, nq, rows_img, rows16, rows16l, hd16, (long long)n, (unsigned)row_base, (int)(bps * 64), t0, t0_stride, parts, qc);
-        } else if (k2p == 8) hipLaunchKernelGGL(k_l2_topk_mfma<8>, dim3(slices, qtiles), dim3(256), 0, s, q, nq, rows_img, hd, (long long)n, (unsigned)row_base, (int)(bps * 64), t0, t0_stride, parts);
-        else hipLaunchKernelGGL(k_l2_topk_mfma<16>, dim3(slices, qtiles), dim3(256), 0, s, q, nq, rows_img, hd, (long long)n, (unsigned)row_base, (int)(bps * 64), t0, t0_stride, parts);
         RF_CHECK_LAUNCH("rf_l2_topk(mfma scan)");
     } else {
+        // enough workgroups to fill 256 CUs a few times over, at least 4 blocks per list
         const int qtiles = (nq + RF_TQ - 1) / RF_TQ;
-        // enough workgroups to fill 256 CUs a few times over, at most 64 slices (= lists per query to merge), at least 4 blocks per list
-        long long sl = (1024 + qtiles - 1) / qtiles;
-        if (sl > 64) sl = 64;
-        if (sl > (nblk + 3) / 4) sl = (nblk + 3) / 4;
-        if (sl < 1) sl = 1;
-        const int bps = (int)((nblk + sl - 1) / sl);
-        slices = (int)((nblk + bps - 1) / bps);
-        if (k2p == 8) hipLaunchKernelGGL(k_l2_topk<8>, dim3(slices, qtiles), dim3(256), 0, s, q, nq, db_packed, (long long)n, (unsigned)row_base, bps, parts);
-        else hipLaunchKernelGGL(k_l2_topk<16>, dim3(slices, qtiles), dim3(256), 0, s, q, nq, db_packed, (long long)n, (unsigned)row_base, bps, parts);
+        sl = topk_slices(nblk, qtiles, 1024, (nblk + 3) / 4);
+        RF_LAUNCH_K2(k_l2_topk, k2p, dim3(sl.count, qtiles), s, q, nq, db_packed, (long long)n, (unsigned)row_base, (int)sl.per, parts);
         RF_CHECK_LAUNCH("rf_l2_topk(scan)");
     }
     // merge the per-slice lists (each k2p wide) and emit the first k2
-    return launch_merge(parts, slices, nq, k2p, k2, out_dist, out_idx, out_keys, s, "rf_l2_topk(merge)");
+    return launch_merge(parts, sl.count, nq, k2p, k2, out_dist, out_idx, out_keys, s, "rf_l2_topk(merge)");
 }
 
 extern "C" int rf_l2_topk(const float* q, int nq, int dim, const float* db_packed, int64_t n, int64_t row_base, int k2, int algo,

@@ -755,9 +755,11 @@ def check_topk(idx_got, dist_got, q, emb, k2, row_base=0):
 
 
 @pytest.mark.parametrize('algo', [1, 2, 3])
-@pytest.mark.parametrize('n,nq,k2', [(1000, 64, 8), (50_001, 128, 8), (4097, 70, 16), (5, 3, 8), (64, 1, 8), (131, 300, 8)])
+@pytest.mark.parametrize('n,nq,k2', [(1000, 64, 8), (50_001, 128, 8), (4097, 70, 16), (5, 3, 8), (64, 1, 8), (131, 300, 8), (90, 70, 8), (190, 5, 16)])
 def test_l2_topk(ops, n, nq, k2, algo):
-    """the scans (1 = VALU, every pair exact; 2 / 3 = fp32- / f16-MFMA dot-product filter + exact re-check) against the float64 oracle"""
+    """the scans (1 = VALU, every pair exact; 2 / 3 = fp32- / f16-MFMA dot-product filter + exact re-check) against the float64 oracle.
+    The small shapes walk every exit of the filtered scans' tile pipelines (32-row tiles; two tiles in flight for algo 2 and the seed, three for
+    algo 3): 1, 2, 4, 5 and 6 tiles per slice, and -- (90, 70, 8), (190, 5, 16) -- 3 and 6 tiles in ONE slice."""
     rng = np.random.default_rng(n + nq)
     emb = rng.standard_normal((n, 64)).astype(np.float32)
     emb /= np.linalg.norm(emb, axis=1, keepdims=True)
