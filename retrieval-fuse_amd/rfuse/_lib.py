@@ -1,4 +1,5 @@
-"""ctypes binding of librfuse_hip.so (the C ABI declared in include/rfuse.h, and the evaluation ABI of include/rfuse_eval.h).
+"""ctypes binding of librfuse_hip.so (the C ABI declared in include/rfuse.h, the evaluation ABI of include/rfuse_eval.h and the training-loss ABI
+of include/rfuse_train.h).
 
 The argument and return types are read from the header itself at import (``parse_header``): there is no second copy of the ABI to keep
 in step.  There is NO fallback: if the library is missing a RuntimeError is raised, and every entry point that returns a status
@@ -6,7 +7,8 @@ in step.  There is NO fallback: if the library is missing a RuntimeError is rais
 first so that the HIP runtime the library binds to is the one PyTorch-ROCm already loaded (same SONAME).
 
 ``load()`` binds include/rfuse.h (``SIGNATURES``; the profiling wrapper brackets these); ``load_eval()`` binds include/rfuse_eval.h
-(``EVAL_SIGNATURES``: the mesh metrics, rfuse/mesh_metrics.py) from the same shared object, under the same status rule.
+(``EVAL_SIGNATURES``: the mesh metrics, rfuse/mesh_metrics.py) and ``load_train()`` include/rfuse_train.h (``TRAIN_SIGNATURES``: the shape loss,
+rfuse/losses.py), both from the same shared object, under the same status rule.
 """
 import ctypes
 import os
@@ -19,6 +21,7 @@ _HERE = Path(__file__).resolve().parent
 LIB_PATH = Path(os.environ.get('RFUSE_LIB', _HERE / 'librfuse_hip.so'))
 HEADER_PATH = _HERE.parents[1] / 'include' / 'rfuse.h'
 EVAL_HEADER_PATH = _HERE.parents[1] / 'include' / 'rfuse_eval.h'
+TRAIN_HEADER_PATH = _HERE.parents[1] / 'include' / 'rfuse_train.h'
 
 # every scalar type include/rfuse.h uses; any pointer is a c_void_p, and `const char*` as a return type a c_char_p
 _SCALARS = {'int': ctypes.c_int, 'float': ctypes.c_float, 'size_t': ctypes.c_size_t, 'int64_t': ctypes.c_int64, 'long long': ctypes.c_int64}
@@ -67,6 +70,7 @@ def parse_header(text):
 # name -> (restype, argtypes, parameter names): include/rfuse.h is the only description of the ABI
 SIGNATURES = parse_header(HEADER_PATH.read_text())
 EVAL_SIGNATURES = parse_header(EVAL_HEADER_PATH.read_text())
+TRAIN_SIGNATURES = parse_header(TRAIN_HEADER_PATH.read_text())
 
 
 def is_status(name, table=None):
@@ -83,6 +87,7 @@ def _raise_on_status(rc, fn, args):
 
 _lib = None
 _eval = None
+_train = None
 
 
 class _Library:
@@ -144,6 +149,14 @@ def load_eval():
     if _eval is None:
         _eval = _Library(load()._cdll, EVAL_SIGNATURES)
     return _eval
+
+
+def load_train():
+    """The entry points of include/rfuse_train.h, bound like ``load_eval()``'s."""
+    global _train
+    if _train is None:
+        _train = _Library(load()._cdll, TRAIN_SIGNATURES)
+    return _train
 
 
 def check(rc, what):
