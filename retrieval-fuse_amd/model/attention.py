@@ -17,7 +17,7 @@ import math
 import torch
 from torch import nn
 
-from rfuse import ops
+from rfuse import ops, routes
 
 
 class LinearParams(nn.Module):
@@ -69,7 +69,7 @@ class AttentionFeatureEncoder(nn.Module):
 
     def fusable(self):
         """True when the 4 layers fit the fused MFMA kernel (rf_attn_mlp_*): n_in a multiple of 16 up to 128, 32 outputs."""
-        return ops.USE_FUSED_ATTN_MLP and self.n_in % 16 == 0 and 16 <= self.n_in <= 128 and self.n_out == 32
+        return routes.attn_mlp_fused(self.n_in, self.n_out)
 
     def packed_fused(self):
         return self._fused.get([self.encoder[i] for i in (0, 2, 4, 6)])

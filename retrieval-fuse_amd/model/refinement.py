@@ -5,8 +5,8 @@ import math
 import torch
 from torch import nn
 
-from model.unet import UNet3D, DecoderNoJoining, _group_elements
-from rfuse import ops
+from model.unet import UNet3D, DecoderNoJoining
+from rfuse import ops, routes
 
 
 def _unet(width, out_channels, order, levels, f_maps=None, trim=0):
@@ -99,22 +99,18 @@ class Superresolution08FinalDecoder(nn.Module):
         """the up stage's second conv + the pointwise head (+ network_pred_to_df).  Where the split box kernel takes the conv, the head runs in its epilogue:
         the nf-channel 64^3 tensor (0.5 GB per 32 chunks) is neither written nor read back."""
         dc = self.network[0].basic_module
-        c1, c2, pw = dc.SingleConv1, dc.SingleConv2, self.network[1]
-        g1, g2 = c1.groupnorm, c2.groupnorm
-        cmid, cout2, edge2 = c1.conv.out_channels, c2.conv.out_channels, 2 * x.shape[2]
-        if (ops.conv_up_split_ch8_supported(x, cmid, cout2)
-                and ops.split_range_ok(c1.conv.weight, g1.weight, g1.bias, _group_elements(g1, edge2))
-                and ops.split_range_ok(c2.conv.weight, g2.weight, g2.bias, _group_elements(g2, edge2))):
+        c1, c2, pw, g1, g2 = dc.SingleConv1, dc.SingleConv2, self.network[1], dc.SingleConv1.groupnorm, dc.SingleConv2.groupnorm
+        n, cmid, cout, edge = x.shape[0], c1.conv.out_channels, c2.conv.out_channels, 2 * x.shape[2]
+        route = routes.head(n, x.shape[1], edge, cmid, cout, c1.range_ok(edge), c2.range_ok(edge))
+        if route == 'ch8':
             # both convs on 8^3 boxes of the 64^3 volume: the first writes its output channel-interleaved (8 channels of a voxel together), which is how the
             # second stages it -- two 16-byte loads per voxel instead of eight 4-byte gathers; the second GroupNorm comes from the first's per-box sums
             aff1 = ops.gn_affine(None, x, g1.weight, g1.bias, g1.num_groups, g1.eps)
             y1c, stats, tiles = ops.conv3d_up_split_gn_relu_ch8(x, aff1, c1.conv.packed_up_split(0), cmid)
-            aff2 = ops.gn_affine_from_stats(stats, tiles, x.shape[0], cmid, edge2, g2.weight, g2.bias, g2.num_groups, g2.eps)
-            return ops.conv3d_split_pointwise_tanh_ch8(y1c, aff2, c2.conv.packed_split(), cout2, pw.weight, pw.bias, post_add, post_mul)
+            aff2 = ops.gn_affine_from_stats(stats, tiles, n, cmid, edge, g2.weight, g2.bias, g2.num_groups, g2.eps)
+            return ops.conv3d_split_pointwise_tanh_ch8(y1c, aff2, c2.conv.packed_split(), cout, pw.weight, pw.bias, post_add, post_mul)
         y1 = c1(None, x)
-        cout, edge = c2.conv.out_channels, y1.shape[2]
-        if (ops.conv_split_pointwise_supported(y1, cout)
-                and ops.split_range_ok(c2.conv.weight, g2.weight, g2.bias, _group_elements(g2, edge))):
+        if route == 'pointwise':
             aff = ops.gn_affine(y1, None, g2.weight, g2.bias, g2.num_groups, g2.eps)
             return ops.conv3d_split_pointwise_tanh(y1, aff, c2.conv.packed_split(), cout, pw.weight, pw.bias, post_add, post_mul)
         return ops.conv1x1_tanh(c2(y1), pw.weight, pw.bias, post_add=post_add, post_mul=post_mul)

@@ -8,9 +8,8 @@ so ``model.get_retrieval_networks`` (reference model/__init__.py:6-38) keeps wor
   MLP family   (Patch04 :64-84, Patch05 :87-107, Patch04V2 :110-132): rf_linear (fp32 MFMA) with fused ReLU
   conv family  (Patch08 :136-156, Patch12 :364-388, Patch16 :277-303, Patch24 :306-332, Patch24V2 :335-361,
                 Patch32 :4-28, PCPatch32 :187-213, PCPatch48 :217-243, PCPatch64 :247-273):
-                rf_conv3d_valid_leaky_valu (first layers: packed-fp32 VALU) / _lds (large layers: LDS-staged MFMA) / _mfma (small ones:
-                gather-form MFMA) -- valid
-                strided conv + bias + LeakyReLU 0.2 on the fp32 matrix cores -- then rf_linear for final_layer
+                valid strided conv + bias + LeakyReLU 0.2 in the form rfuse.routes.valid names (split-operand F16 MFMA, tiled or as a persistent grid /
+                packed-fp32 VALU for first layers / LDS-staged or gather-form fp32 MFMA) -- then rf_linear for final_layer
 
 The two BatchNorm variants (PatchNorm08 :160-184, PatchNorm32 :31-61) construct and serialise identically but their
 forward is not built: no shipped config selects them.
@@ -24,7 +23,7 @@ from torch import nn
 
 from model.attention import LinearParams, ActivationMarker
 from model.unet import Conv3dParams
-from rfuse import autograd, ops
+from rfuse import autograd, ops, routes
 
 
 class _MLPPatchEncoder(nn.Module):
@@ -100,31 +99,23 @@ class _ConvPatchEncoder(nn.Module):
         self.final_layer = LinearParams(self.SPEC[-1][1] * nf, z_dim)
 
     @staticmethod
-    def _split_takes(layer, shape):
-        """does `layer` run as the split-operand F16-MFMA form on an input of shape (n, cin, edge)?"""
-        return (ops.CONV_ARITH == 'split' and layer.in_channels % 4 == 0 and ops.split_range_ok(layer.weight)
-                and bool(ops._lib.load().rf_conv3d_valid_split_supported(max(shape[0], 1), shape[1], shape[2], layer.out_channels, layer.kernel_size, layer.stride)))
+    def _ask(layer, shape):
+        """`layer` on an input of shape (n, cin, edge, ...) as rfuse.routes.valid's tuple"""
+        return shape[0], shape[1], shape[2], layer.out_channels, layer.kernel_size, layer.stride, lambda: ops.split_range_ok(layer.weight)
 
-    @staticmethod
-    def _valu_takes(layer, shape):
-        return ops.USE_CONVV_VALU and bool(ops._lib.load().rf_conv3d_valid_valu_supported(max(shape[0], 1), shape[1], shape[2], layer.out_channels, layer.kernel_size,
-                                                                                             layer.stride))
-
-    def _conv(self, layer, x, out_split=False):
-        """one conv + bias + LeakyReLU; `x` fp32 or ops.SplitActs; out_split: leave the output in split form (the caller knows the next layer reads it)"""
-        shape = (x.shape[0], x.shape[1], x.shape[2])
-        if isinstance(x, ops.SplitActs) and out_split and ops.conv_valid_split_pg_supported(shape, layer.out_channels, layer.kernel_size, layer.stride) \
-                and ops.split_range_ok(layer.weight):
-            return ops.conv3d_valid_leaky_split_pg(x, layer.packed_valid_split_pg(x.shape[2]), layer.bias, layer.out_channels, layer.kernel_size, layer.stride, 0.2)
-        if isinstance(x, ops.SplitActs) or self._split_takes(layer, shape):
-            return ops.conv3d_valid_leaky_split(x, layer.packed_valid_split(x.shape[2]), layer.bias, layer.out_channels, layer.kernel_size, layer.stride, 0.2,
-                                                out_split=out_split)
-        if self._valu_takes(layer, shape):
-            return ops.conv3d_valid_leaky_valu(x, layer.packed_valu(), layer.bias, layer.stride, 0.2, out_split=out_split)
-        assert not out_split
-        if ops.conv_valid_lds_supported(x, layer.out_channels, layer.kernel_size, layer.stride):
-            return ops.conv3d_valid_leaky_lds(x, layer.packed_lds(), layer.bias, layer.out_channels, layer.kernel_size, layer.stride, 0.2)
-        return ops.conv3d_valid_leaky_mfma(x, layer.packed(), layer.bias, layer.out_channels, layer.kernel_size, layer.stride, 0.2)
+    def _conv(self, layer, x, nxt=None):
+        """one conv + bias + LeakyReLU; `x` fp32 or ops.SplitActs; nxt: self._ask(next layer, its input shape) where the output goes to it (split form: see _run)"""
+        form, out_split = routes.valid(self._ask(layer, x.shape), isinstance(x, ops.SplitActs), nxt)
+        cout, k, stride = layer.out_channels, layer.kernel_size, layer.stride
+        if form == 'grid':
+            return ops.conv3d_valid_leaky_split_pg(x, layer.packed_valid_split_pg(x.shape[2]), layer.bias, cout, k, stride, 0.2)
+        if form == 'split':
+            return ops.conv3d_valid_leaky_split(x, layer.packed_valid_split(x.shape[2]), layer.bias, cout, k, stride, 0.2, out_split=out_split)
+        if form == 'valu':
+            return ops.conv3d_valid_leaky_valu(x, layer.packed_valu(), layer.bias, stride, 0.2, out_split=out_split)
+        if form == 'lds':
+            return ops.conv3d_valid_leaky_lds(x, layer.packed_lds(), layer.bias, cout, k, stride, 0.2)
+        return ops.conv3d_valid_leaky_mfma(x, layer.packed(), layer.bias, cout, k, stride, 0.2)
 
     def _run(self, convs, x, cut=None):
         """The conv layers in order on x.  cut = (index, window edge, lattice step, windows per axis): behind layer `index` the windows are cut out of the
@@ -132,14 +123,10 @@ class _ConvPatchEncoder(nn.Module):
         couts in fours) and the consumer is a split-operand layer: no GroupNorm sits between the encoders' convs, so what the consumer would make
         of every value it stages (scale, clamp, split -- with its halo, three times per value) the producer makes once."""
         for i, layer in enumerate(convs):
-            shape = (x.shape[0], x.shape[1], x.shape[2])
-            so = (shape[2] - layer.kernel_size) // layer.stride + 1
+            so = (x.shape[2] - layer.kernel_size) // layer.stride + 1
             cut_here = cut is not None and cut[0] == i
-            next_shape = (shape[0] * cut[3] ** 3, layer.out_channels, cut[1]) if cut_here else (shape[0], layer.out_channels, so)
-            writes_split = (ops.USE_SPLIT_CHAIN and i + 1 < len(convs) and layer.out_channels % 4 == 0
-                            and (isinstance(x, ops.SplitActs) or self._split_takes(layer, shape) or self._valu_takes(layer, shape))
-                            and self._split_takes(convs[i + 1], next_shape))
-            x = self._conv(layer, x, out_split=writes_split)
+            next_shape = (x.shape[0] * cut[3] ** 3, layer.out_channels, cut[1]) if cut_here else (x.shape[0], layer.out_channels, so)
+            x = self._conv(layer, x, self._ask(convs[i + 1], next_shape) if i + 1 < len(convs) else None)
             if cut_here:
                 x = ops.gather_windows(x, cut[1], cut[2], cut[3])
         return x
@@ -205,7 +192,7 @@ class _ConvPatchEncoder(nn.Module):
         sw, lat, done = window, step, 0
         shape = (grid.shape[0], 1, g)
         for layer in convs[:on_grid]:
-            if not (self._split_takes(layer, shape) or self._valu_takes(layer, shape)):
+            if routes.valid(self._ask(layer, shape), False, fp32_forms=False)[0] is None:
                 break
             sw, lat, done = (sw - layer.kernel_size) // layer.stride + 1, lat // layer.stride, done + 1
             shape = (shape[0], layer.out_channels, (shape[2] - layer.kernel_size) // layer.stride + 1)

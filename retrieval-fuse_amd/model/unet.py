@@ -2,22 +2,17 @@
 
 Same class names, constructor arguments and ``state_dict`` keys as the reference (model/unet.py:79-100 SingleConv,
 :103-144 DoubleConv, :147-159 StepDownDoubleConv, :210-253 Encoder, :256-322 Decoder/DecoderNoJoining, :392-537
-Abstract3DUNet/UNet3D), so reference checkpoints load unchanged.  The modules only HOLD parameters; ``forward`` runs
-the gfx950 kernels of librfuse_hip.so through ``rfuse.ops``:
-
-  SingleConv('gcr')  = rf_gn_stats / rf_gn_from_stats  +  rf_conv3d_k3_gn_relu  (GroupNorm apply, upsample+concat read, ReLU fused in)
-  Encoder pooling    = rf_maxpool3d_2
-  Decoder upsample + concat: never materialised -- the conv reads (skip, low-res) as two sources.
-
-Only layer order 'gcr' with DoubleConv is implemented: it is the only path any shipped config reaches (SURVEY.md 2,
-row 1).  Inference only (no autograd); CPU tensors raise.
+Abstract3DUNet/UNet3D), so reference checkpoints load unchanged.  The modules HOLD the parameters and their packed weight images; a
+``forward`` asks ``rfuse.routes`` which kernel form takes the layer (or the conv pair: DESIGN 4.8 / 4.9) and runs the form it names through ``rfuse.ops``
+-- GroupNorm applied in the conv's prologue, ReLU, max-pool and statistics for the next GroupNorm in its epilogue, a decoder's upsample + concat read as two
+sources.  Only layer order 'gcr' is built; in grad mode SingleConv runs rfuse/autograd.py (no hand-overs); CPU tensors raise.
 """
 import math
 
 import torch
 from torch import nn
 
-from rfuse import ops
+from rfuse import ops, routes
 
 
 class GroupNormParams(nn.Module):
@@ -103,16 +98,6 @@ class Conv3dParams(nn.Module):
         return f'{self.in_channels}, {self.out_channels}, kernel_size={self.kernel_size}, stride={self.stride}, padding={self.padding}'
 
 
-def _groups_of(gn):
-    """the group count GroupNormParams really normalises with (reference model/unet.py:62-63: one group when there are fewer channels than groups)"""
-    return 1 if gn.num_channels < gn.num_groups else gn.num_groups
-
-
-def _group_elements(gn, edge):
-    """elements one GroupNorm group holds on an edge^3 volume (the bound on |GroupNorm output| that ops.split_range_ok checks is gamma * sqrt(that) + |beta|)"""
-    return (gn.num_channels // _groups_of(gn)) * edge ** 3
-
-
 class SingleConv(nn.Module):
     """GroupNorm -> Conv3d(k3, p1, no bias) -> ReLU, order 'gcr' (reference model/unet.py:19-76,79-100)."""
 
@@ -125,101 +110,105 @@ class SingleConv(nn.Module):
         self.groupnorm = GroupNormParams(num_groups, in_channels)
         self.conv = Conv3dParams(in_channels, out_channels, 3, bias=False, padding=1)
 
-    def forward(self, x, upsampled=None, _direct=False, pool=None):
+    def range_ok(self, edge):
+        """as a callable for rfuse.routes: can the split-operand forms not saturate on an edge^3 input (ops.split_range_ok: |gamma| sqrt(group elements) + |beta|)"""
+        gn = self.groupnorm
+        return lambda: ops.split_range_ok(self.conv.weight, gn.weight, gn.bias, (gn.num_channels // gn.num_groups) * edge ** 3)
+
+    def forward(self, x, upsampled=None, pool=None):
         """x: full-resolution source [N,C0,S,S,S] or None; ``upsampled``: low-resolution source [N,C1,S/2,S/2,S/2] that the
         reference would nearest-upsample and concatenate after x (model/unet.py:297-308).
-
         ``pool``: None -> returns the output; 'also' / 'only' -> returns (output, MaxPool3d(2)(output)) with the pooling
         fused into the conv epilogue where the tiling allows ('only': the caller never reads the full-resolution output, which
         is then not written at all and returned as None)."""
-        gn = self.groupnorm
-        cout = self.conv.out_channels
-        if ops.needs_grad(x, upsampled, self.conv.weight, gn.weight, gn.bias):
+        gn, conv, cout = self.groupnorm, self.conv, self.conv.out_channels
+        if ops.needs_grad(x, upsampled, conv.weight, gn.weight, gn.bias):
             # training slice (SURVEY 8f N4): the same kernels behind torch.autograd.Function, see rfuse/autograd.py
             from rfuse import autograd as rf_autograd
-            out = rf_autograd.conv_gn_relu(x, upsampled, gn.weight, gn.bias, self.conv.weight, gn.num_groups, gn.eps)
+            out = rf_autograd.conv_gn_relu(x, upsampled, gn.weight, gn.bias, conv.weight, gn.num_groups, gn.eps)
             return out if pool is None else (out, rf_autograd.max_pool2(out))
         aff = ops.gn_affine(x, upsampled, gn.weight, gn.bias, gn.num_groups, gn.eps)
-        edge = x.shape[2] if x is not None else 2 * upsampled.shape[2]
-        # the split-operand (F16 matrix core) forms only where they cannot saturate: weights and GroupNorm outputs inside the f16 pair's range
-        # (ops.split_range_ok, decided from the parameters once per version); otherwise the fp32 kernels, like the reference's fp32 path
-        split_ok = ops.CONV_ARITH == 'split' and ops.split_range_ok(self.conv.weight, gn.weight, gn.bias, _group_elements(gn, edge))
-        if not split_ok:
-            return self._forward_fp32(x, upsampled, aff, cout, edge, _direct, pool)
-        if upsampled is None and not _direct and ops.conv_split_supported(x, None, cout):
-            return ops.conv3d_split_gn_relu(x, aff, self.conv.packed_split(), cout, pool=pool)
-        if upsampled is None and not _direct and edge <= 2 and ops.conv_e2_split_supported(x, cout):
-            out = ops.conv3d_e2_split_gn_relu(x, aff, self.conv.packed_e2_split(edge), cout)
-            return out if pool is None else (out, ops.maxpool2(out))
-        if upsampled is not None and edge == 2 and not _direct and pool is None:
-            # decoder stage on 2^3 volumes (skip @2^3 + a 1^3 source): the eight copies of the low-resolution voxel written out (a [n][c0 + c1][8] tensor, a
-            # few KB per sample) and the layer run as the dense GEMM -- the affine table is per channel of the concatenation either way
-            up = upsampled.reshape(upsampled.shape[0], upsampled.shape[1], 1, 1, 1).expand(-1, -1, 2, 2, 2)
+        n, c0, c1, edge = ops._src_dims(x, upsampled)
+        route = routes.single(n, c0, c1, edge, cout, pool, routes.split_arith(self.range_ok(edge)), materialised=False)
+        if route == 'split_box':
+            return ops.conv3d_split_gn_relu(x, aff, conv.packed_split(), cout, pool=pool)
+        if route == 'pool_fp32':
+            return ops.conv3d_gn_relu_pool(x, None, aff, conv.packed(), cout, keep_full=(pool == 'also'))
+        if route == 'e2':
+            out = ops.conv3d_e2_split_gn_relu(x, aff, conv.packed_e2_split(edge), cout)
+        elif route == 'e2_concat':
+            # decoder stage on 2^3 volumes (skip @2^3 + a 1^3 source): the eight copies of the low-resolution voxel written out (a few KB per sample), dense GEMM
+            up = upsampled.reshape(n, c1, 1, 1, 1).expand(-1, -1, 2, 2, 2)
             xc = torch.cat((x, up), dim=1) if x is not None else up.contiguous()
-            if ops.conv_e2_split_supported(xc, cout):
-                return ops.conv3d_e2_split_gn_relu(xc, aff, self.conv.packed_e2_split(2), cout)
-        if pool is not None and upsampled is None and not _direct and edge >= 4 and ops.conv_pool_supported(x, None, cout):
-            return ops.conv3d_gn_relu_pool(x, None, aff, self.conv.packed(), cout, keep_full=(pool == 'also'))
-        if _direct or edge == 1:
-            out = ops.conv3d_gn_relu(x, upsampled, aff, None, cout, direct_weight=self.conv.weight)
-        elif ops.conv_up_split_supported(x, upsampled, cout):
-            c0 = x.shape[1] if x is not None else 0
-            out = ops.conv3d_up_split_gn_relu(x, upsampled, aff, self.conv.packed_up_split(c0), cout)
-        elif upsampled is not None and edge >= 8 and ops.conv_split_supported_shape(upsampled.shape[0], (x.shape[1] if x is not None else 0) + upsampled.shape[1], edge, cout):
-            # a decoder stage outside the decoder forms of the F16 cores (C5's 96 + 192 -> 96 @16^3 at 16 chunks: 192 upsampled channels, 128 boxes): the
-            # concatenation written out once (as for the 2^3 stage above; 75 MB there) and the layer run by the split-operand box kernel with its cout blocks
-            # on grid.y -- 0.53 ms as the fp32-MFMA decoder form.  The affine table is per channel of the concatenation either way.
+            out = ops.conv3d_e2_split_gn_relu(xc, aff, conv.packed_e2_split(2), cout)
+        elif route == 'direct':
+            out = ops.conv3d_gn_relu(x, upsampled, aff, None, cout, direct_weight=conv.weight)
+        elif route == 'up_split':
+            out = ops.conv3d_up_split_gn_relu(x, upsampled, aff, conv.packed_up_split(c0), cout)
+        elif route == 'split_box_concat':
+            # a decoder stage outside the decoder forms of the F16 cores (C5's 96 + 192 -> 96 @16^3 at 16 chunks): the concatenation written out once (75 MB
+            # there) for the split-operand box kernel -- 0.53 ms as the fp32-MFMA decoder form.  The affine table is per channel of the concatenation either way.
             up = upsampled.repeat_interleave(2, dim=2).repeat_interleave(2, dim=3).repeat_interleave(2, dim=4)
-            xc = torch.cat((x, up), dim=1) if x is not None else up
-            out = ops.conv3d_split_gn_relu(xc, aff, self.conv.packed_split(), cout)
-        elif ops.conv_up_supported(x, upsampled, cout):
-            c0 = x.shape[1] if x is not None else 0
-            out = ops.conv3d_up_gn_relu(x, upsampled, aff, self.conv.packed_up(c0), cout)
+            out = ops.conv3d_split_gn_relu(torch.cat((x, up), dim=1) if x is not None else up, aff, conv.packed_split(), cout)
+        elif route == 'up_fp32':
+            out = ops.conv3d_up_gn_relu(x, upsampled, aff, conv.packed_up(c0), cout)
         else:
-            out = ops.conv3d_gn_relu(x, upsampled, aff, self.conv.packed(), cout)
-        return out if pool is None else (out, ops.maxpool2(out))
-
-    def _forward_fp32(self, x, upsampled, aff, cout, edge, _direct, pool):
-        """the same layer on the fp32-MFMA kernels only (a parameter outside the split forms' range)"""
-        if pool is not None and upsampled is None and not _direct and edge >= 4 and ops.conv_pool_supported(x, None, cout):
-            return ops.conv3d_gn_relu_pool(x, None, aff, self.conv.packed(), cout, keep_full=(pool == 'also'))
-        if _direct or edge == 1:
-            out = ops.conv3d_gn_relu(x, upsampled, aff, None, cout, direct_weight=self.conv.weight)
-        elif ops.conv_up_supported(x, upsampled, cout):
-            out = ops.conv3d_up_gn_relu(x, upsampled, aff, self.conv.packed_up(x.shape[1] if x is not None else 0), cout)
-        else:
-            out = ops.conv3d_gn_relu(x, upsampled, aff, self.conv.packed(), cout)
+            out = ops.conv3d_gn_relu(x, upsampled, aff, conv.packed(), cout)
         return out if pool is None else (out, ops.maxpool2(out))
 
 
+class _ConvPair(nn.Module):
+    """SingleConv1 -> SingleConv2; where rfuse.routes.pair says so the first hands the second its input pre-split."""
+    ENCODER_FORMS = True
+
+    def route(self, x, upsampled=None, pool=None, next_block=None):
+        """the name rfuse.routes.pair gives this block's form on these inputs (arguments as forward's)"""
+        if isinstance(x, ops.PreSplit):
+            return 'prepooled'                                      # its producer asked (accepts_prepooled) before it wrote
+        c1, c2 = self.SingleConv1, self.SingleConv2
+        (n, ch0, ch1, edge), cout = ops._src_dims(x, upsampled), c2.conv.out_channels
+        grad = ops.needs_grad(x, upsampled, c1.conv.weight, c2.conv.weight, c1.groupnorm.weight, c2.groupnorm.weight)
+        return routes.pair(n, ch0, ch1, edge, c1.conv.out_channels, cout, c2.groupnorm.num_groups, pool, grad, c1.range_ok(edge), c2.range_ok(edge),
+                           encoder_forms=self.ENCODER_FORMS, next_takes=None if next_block is None else (lambda: next_block.accepts_prepooled(n, cout, edge // 2)),
+                           next_groups=0 if next_block is None else next_block.SingleConv1.groupnorm.num_groups)
+
+    def accepts_prepooled(self, n, cin, edge):
+        """this block's conv pair can take its input as an ops.PreSplit of [n, cin, edge^3] (normalised for SingleConv1's GroupNorm) -- decided from shapes and
+        parameters only, so that the PRODUCER can ask before it writes"""
+        c1, c2 = self.SingleConv1, self.SingleConv2
+        grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        return c1.conv.in_channels == cin and routes.pair(n, cin, 0, edge, c1.conv.out_channels, c2.conv.out_channels, c2.groupnorm.num_groups, None, grad,
+                                                          c1.range_ok(edge), c2.range_ok(edge), offered=True) == 'prepooled'
+
+    def forward(self, x, upsampled=None, pool=None, next_block=None):
+        """``next_block``: the DoubleConv that will read MaxPool3d(2) of this block's output (the next encoder level), when the caller knows it -- with
+        pool='only' the pooled tensor can then be handed over pre-split (returned as an ops.PreSplit in place of the pooled tensor)."""
+        c1, c2 = self.SingleConv1, self.SingleConv2
+        route = self.route(x, upsampled, pool, next_block)
+        if route == 'plain':
+            return c2(c1(x, upsampled), pool=pool)
+        # a producer that applies the SECOND GroupNorm to its own output and writes it pre-split (no fp32 intermediate, no rf_gn_from_stats), then the consumer
+        g1, g2, cmid, cout, pm = c1.groupnorm, c2.groupnorm, c1.conv.out_channels, c2.conv.out_channels, route == 'decoder_presplit_pm'
+        second = (g2.weight, g2.bias, g2.num_groups, g2.eps)
+        if route == 'prepooled':                                    # the previous level handed its pooled output over pre-split for THIS block's first GroupNorm
+            n, edge, pre = x.n, x.edge, ops.conv3d_split_pre_presplit(x, c1.conv.packed_split(), cmid, *second).data
+        else:
+            n, ch0, _, edge = ops._src_dims(x, upsampled)
+            if route in ('cin1_presplit', 'cin1_presplit_handed'):  # level 0 of a U-Net on 16^3 samples: the 1-channel conv computes its own GroupNorm
+                pre = ops.conv3d_cin1_presplit(x, g1.weight, g1.bias, g1.eps, c1.conv.packed(), cmid, *second)
+            else:
+                aff = ops.gn_affine(x, upsampled, g1.weight, g1.bias, g1.num_groups, g1.eps)
+                if route == 'box_presplit':                         # an encoder level on whole 8^3 samples (16 -> 16 -> 32 of the retrieval backbone)
+                    pre = ops.conv3d_split_presplit(x, aff, c1.conv.packed_split(), cmid, *second)
+                else:                                               # a decoder's pair on whole 8^3 samples; parity-major where producer and consumer are persistent
+                    pre = ops.conv3d_up_split_presplit(x, upsampled, aff, c1.conv.packed_up_split(ch0), cmid, *second, parity_major=pm)
+        if route == 'cin1_presplit_handed':                         # -> (None, the pooled output as an ops.PreSplit for next_block)
+            ng = next_block.SingleConv1.groupnorm
+            return ops.conv3d_split_pre_relu_pool_presplit(pre, cmid, n, edge, c2.conv.packed_split(), cout, ng.weight, ng.bias, ng.num_groups, ng.eps)
+        return ops.conv3d_split_pre_relu(pre, cmid, n, edge, c2.conv.packed_split(), cout, pool=pool, parity_major=pm)
 
 
-def _decoder_pair_presplit_ok(c1, c2, x, upsampled):
-    """A decoder's conv pair on whole 8^3 samples: the first conv (decoder form, split operands) sees the whole sample, so it can apply the SECOND
-    conv's GroupNorm to its own output and hand it over pre-split: no fp32 intermediate, no rf_gn_from_stats, the second conv stages copies."""
-    g1, g2 = c1.groupnorm, c2.groupnorm
-    if ops.needs_grad(x, upsampled, c1.conv.weight, c2.conv.weight, g1.weight, g2.weight):
-        return False
-    cmid, n, edge = c1.conv.out_channels, upsampled.shape[0], 2 * upsampled.shape[2]
-    if not ops.conv_up_split_presplit_supported(x, upsampled, cmid, _groups_of(g2)):
-        return False
-    if not bool(ops._lib.load().rf_conv3d_split_pre_supported(cmid, n, edge, c2.conv.out_channels)):
-        return False
-    return (ops.split_range_ok(c1.conv.weight, g1.weight, g1.bias, _group_elements(g1, edge))
-            and ops.split_range_ok(c2.conv.weight, g2.weight, g2.bias, _group_elements(g2, edge)))
-
-
-def _decoder_pair_presplit(c1, c2, x, upsampled):
-    g1, g2 = c1.groupnorm, c2.groupnorm
-    aff = ops.gn_affine(x, upsampled, g1.weight, g1.bias, g1.num_groups, g1.eps)
-    c0 = x.shape[1] if x is not None else 0
-    # parity-major hand-over where the persistent producer and the persistent consumer both take the shapes (the bench's 8192 patches: k_conv3_up_split_pp)
-    pm = ops.conv_up_split_presplit_pm_supported(x, upsampled, c1.conv.out_channels, _groups_of(g2), c2.conv.out_channels)
-    pre = ops.conv3d_up_split_presplit(x, upsampled, aff, c1.conv.packed_up_split(c0), c1.conv.out_channels, g2.weight, g2.bias, _groups_of(g2), g2.eps, parity_major=pm)
-    return ops.conv3d_split_pre_relu(pre, c1.conv.out_channels, upsampled.shape[0], 2 * upsampled.shape[2], c2.conv.packed_split(), c2.conv.out_channels, parity_major=pm)
-
-
-class DoubleConv(nn.Module):
+class DoubleConv(_ConvPair):
     """Two SingleConvs; channel plan of reference model/unet.py:125-144."""
 
     def __init__(self, in_channels, out_channels, encoder, kernel_size=3, order='gcr', num_groups=8):
@@ -233,76 +222,10 @@ class DoubleConv(nn.Module):
         self.SingleConv1 = SingleConv(c1_in, c1_out, kernel_size, order, num_groups)
         self.SingleConv2 = SingleConv(c2_in, c2_out, kernel_size, order, num_groups)
 
-    def forward(self, x, upsampled=None, pool=None, next_block=None):
-        """``next_block``: the DoubleConv that will read MaxPool3d(2) of this block's output (the next encoder level), when the caller knows it -- with
-        pool='only' the pooled tensor can then be handed over pre-split (returned as an ops.PreSplit in place of the pooled tensor)."""
-        c1, c2 = self.SingleConv1, self.SingleConv2
-        if isinstance(x, ops.PreSplit):
-            # the previous level handed its pooled output over pre-split for THIS block's first GroupNorm: both convs stage copies
-            g2 = c2.groupnorm
-            mid = ops.conv3d_split_pre_presplit(x, c1.conv.packed_split(), c1.conv.out_channels, g2.weight, g2.bias, _groups_of(g2), g2.eps)
-            return ops.conv3d_split_pre_relu(mid.data, mid.channels, mid.n, mid.edge, c2.conv.packed_split(), c2.conv.out_channels, pool=pool)
-        if upsampled is None and self._presplit_ok(x):
-            # level 0 of a U-Net on 16^3 samples: the first conv hands the second its input already normalised (second GroupNorm) and split
-            # into f16 pairs (ops.conv3d_cin1_presplit) -- the second conv stages it with copies (DESIGN 4.8)
-            g1, g2 = c1.groupnorm, c2.groupnorm
-            n, edge, cmid, cout = x.shape[0], x.shape[2], c1.conv.out_channels, c2.conv.out_channels
-            pre = ops.conv3d_cin1_presplit(x, g1.weight, g1.bias, g1.eps, c1.conv.packed(), cmid, g2.weight, g2.bias, g2.num_groups, g2.eps)
-            if pool == 'only' and next_block is not None and next_block.accepts_prepooled(n, cout, edge // 2):
-                ng = next_block.SingleConv1.groupnorm
-                if ops.conv_split_pre_pool_presplit_supported(cmid, n, edge, cout, _groups_of(ng)):
-                    _, handed = ops.conv3d_split_pre_relu_pool_presplit(pre, cmid, n, edge, c2.conv.packed_split(), cout, ng.weight, ng.bias, _groups_of(ng), ng.eps)
-                    return None, handed
-            return ops.conv3d_split_pre_relu(pre, cmid, n, edge, c2.conv.packed_split(), cout, pool=pool)
-        if upsampled is not None and pool is None and _decoder_pair_presplit_ok(c1, c2, x, upsampled):
-            return _decoder_pair_presplit(c1, c2, x, upsampled)
-        if upsampled is None and x is not None and self._box_pair_presplit_ok(x):
-            # an encoder level on whole 8^3 samples (16 -> 16 -> 32 of the retrieval backbone): as above, the producer is the split box kernel
-            g1, g2 = c1.groupnorm, c2.groupnorm
-            aff = ops.gn_affine(x, None, g1.weight, g1.bias, g1.num_groups, g1.eps)
-            pre = ops.conv3d_split_presplit(x, aff, c1.conv.packed_split(), c1.conv.out_channels, g2.weight, g2.bias, _groups_of(g2), g2.eps)
-            return ops.conv3d_split_pre_relu(pre, c1.conv.out_channels, x.shape[0], x.shape[2], c2.conv.packed_split(), c2.conv.out_channels, pool=pool)
-        return c2(c1(x, upsampled), pool=pool)
 
-    def accepts_prepooled(self, n, cin, edge):
-        """this block's conv pair can take its input as an ops.PreSplit of [n, cin, edge^3] (normalised for SingleConv1's GroupNorm) -- decided from shapes and
-        parameters only, so that the PRODUCER can ask before it writes"""
-        c1, c2 = self.SingleConv1, self.SingleConv2
-        g1, g2 = c1.groupnorm, c2.groupnorm
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            return False
-        if c1.conv.in_channels != cin:
-            return False
-        cmid = c1.conv.out_channels
-        if not ops.conv_split_pre_presplit_supported(cin, n, edge, cmid, _groups_of(g2)) or not bool(ops._lib.load().rf_conv3d_split_pre_supported(cmid, n, edge, c2.conv.out_channels)):
-            return False
-        return (ops.split_range_ok(c1.conv.weight, g1.weight, g1.bias, _group_elements(g1, edge))
-                and ops.split_range_ok(c2.conv.weight, g2.weight, g2.bias, _group_elements(g2, edge)))
-
-    def _box_pair_presplit_ok(self, x):
-        c1, c2 = self.SingleConv1, self.SingleConv2
-        g1, g2 = c1.groupnorm, c2.groupnorm
-        if ops.needs_grad(x, c1.conv.weight, c2.conv.weight, g1.weight, g2.weight):
-            return False
-        cmid, n, edge = c1.conv.out_channels, x.shape[0], x.shape[2]
-        if not ops.conv_split_presplit_supported(x, cmid, _groups_of(g2)) or not bool(ops._lib.load().rf_conv3d_split_pre_supported(cmid, n, edge, c2.conv.out_channels)):
-            return False
-        return (ops.split_range_ok(c1.conv.weight, g1.weight, g1.bias, _group_elements(g1, edge))
-                and ops.split_range_ok(c2.conv.weight, g2.weight, g2.bias, _group_elements(g2, edge)))
-
-    def _presplit_ok(self, x):
-        c1, c2 = self.SingleConv1, self.SingleConv2
-        g1, g2 = c1.groupnorm, c2.groupnorm
-        if x is None or ops.needs_grad(x, c1.conv.weight, c2.conv.weight, g1.weight, g2.weight):
-            return False
-        if not ops.cin1_presplit_supported(x, c1.conv.out_channels, g2.num_groups, c2.conv.out_channels):
-            return False
-        edge = x.shape[2]
-        return ops.split_range_ok(c2.conv.weight, g2.weight, g2.bias, _group_elements(g2, edge))
-
-
-class StepDownDoubleConv(nn.Module):
-    """in -> (in+out)//2 -> out (reference model/unet.py:149-159)."""
+class StepDownDoubleConv(_ConvPair):
+    """in -> (in+out)//2 -> out (reference model/unet.py:149-159); a decoder block: of the hand-overs, the decoder pair's only."""
+    ENCODER_FORMS = False
 
     def __init__(self, in_channels, out_channels, encoder, kernel_size=3, order='gcr', num_groups=8):
         super().__init__()
@@ -310,11 +233,6 @@ class StepDownDoubleConv(nn.Module):
         mid = (in_channels + out_channels) // 2
         self.SingleConv1 = SingleConv(in_channels, mid, kernel_size, order, num_groups)
         self.SingleConv2 = SingleConv(mid, out_channels, kernel_size, order, num_groups)
-
-    def forward(self, x, upsampled=None):
-        if upsampled is not None and _decoder_pair_presplit_ok(self.SingleConv1, self.SingleConv2, x, upsampled):
-            return _decoder_pair_presplit(self.SingleConv1, self.SingleConv2, x, upsampled)
-        return self.SingleConv2(self.SingleConv1(x, upsampled))
 
 
 class Encoder(nn.Module):
@@ -339,11 +257,7 @@ class Encoder(nn.Module):
                 x = torch.nn.functional.max_pool3d(x, 2)            # grad mode: torch's max-pool carries the backward
             else:
                 x = ops.maxpool2(x)
-        if pool is None:
-            return self.basic_module(x)
-        if next_block is not None and isinstance(self.basic_module, DoubleConv):
-            return self.basic_module(x, pool=pool, next_block=next_block)
-        return self.basic_module(x, pool=pool)
+        return self.basic_module(x, pool=pool, next_block=next_block)
 
 
 class Decoder(nn.Module):

@@ -4,7 +4,7 @@ The reference trains THROUGH the drop-in modules (trainer/train_refinement.py:41
 retrieval_backbone / attention parameters, :295-306 phase hand-over).  Built here:
 
   ConvGnRelu   y = ReLU(conv3(GroupNorm(x)))   one SingleConv 'gcr' layer (reference model/unet.py:19-76) -- 97 % of the FLOPs
-      forward   rf_gn_stats / rf_gn_from_stats + the inference kernels, chosen like SingleConv.forward chooses them (split-operand F16 forms where
+      forward   rf_gn_stats / rf_gn_from_stats + the inference kernels, chosen by routes.single in its order for a written-out concatenation (split-operand F16 forms where
                 the parameters are inside their range: one batched range check per optimiser step)
       backward  rf_relu_backward[_amax] -> d xn = conv3(dz, W^T with flipped taps), no ReLU: rf_conv3d_split_k3_gn on dz scaled by a power of two
                 into the f16 pairs' range (rf_dgrad_scale_affine; the scale leaves again in the GroupNorm backward), else rf_conv3d_k3_gn (fp32 MFMA)
@@ -16,7 +16,7 @@ retrieval_backbone / attention parameters, :295-306 phase hand-over).  Built her
   MaxPool3d(2) / nearest x2 upsample             rf_maxpool3d_2 + rf_maxpool3d_2_backward, rf_upsample3d_2 + rf_sumpool3d_2 (bit-equal to torch's)
   ConvValidLeaky  y = LeakyReLU(conv_valid(x, W, stride) + b)   one layer of the conv patch encoders (reference model/retrieval.py:4-361), trained
                 with NT-Xent by trainer/train_retrieval.py
-      forward   the inference kernels, chosen per layer like model/retrieval.py:_ConvPatchEncoder._conv chooses them, with an fp32 output (no split
+      forward   the inference kernels, chosen per layer by routes.valid (through model/retrieval.py:_ConvPatchEncoder._conv), with an fp32 output (no split
                 hand-over between layers in grad mode)
       backward  rf_conv3d_valid_leaky_backward (dz from the saved output, db in float64) -> rf_conv3d_valid_dgrad (fp32 MFMA per parity phase; skipped
                 when x needs no gradient: the first layer's input is data) and rf_conv3d_valid_wgrad (fp32 MFMA, split K, float64 slice sum).  fp32
@@ -35,13 +35,9 @@ the queries never train).
 import torch
 import torch.nn.functional as F
 
-from . import _lib, ops
+from . import _lib, ops, routes
 
-_p, _stream = ops._p, ops._stream         # (the helpers below launch on the device of their tensors: ops._device_scoped)
-
-
-def _ws(dev, nbytes):
-    return ops._workspace(dev, nbytes)
+_p, _stream, _ws = ops._p, ops._stream, ops._workspace         # (the helpers below launch on the device of their tensors: ops._device_scoped)
 
 
 @ops._device_scoped
@@ -142,17 +138,18 @@ class ConvGnRelu(torch.autograd.Function):
         with torch.no_grad():
             aff = ops.gn_affine(x, None, gamma, beta, g, eps)
             w = weight.contiguous()
-            # the inference kernels, chosen like model/unet.py:SingleConv.forward chooses them: the split-operand forms where the parameters are
-            # inside their range (one batched range check per optimiser step, ops._abs_max), the fp32 kernels otherwise
-            split_ok = ops.CONV_ARITH == 'split' and ops.split_range_ok(weight, gamma, beta, (cin // g) * edge ** 3)
-            if split_ok and edge <= 2 and ops.conv_e2_split_supported(x, cout):
+            # the inference kernels, in routes.single's order for a written-out concatenation (one batched range check per optimiser step, ops._abs_max)
+            split_ok = routes.split_arith(lambda: ops.split_range_ok(weight, gamma, beta, (cin // g) * edge ** 3))
+            c1 = low.shape[1] if low is not None else 0
+            route = routes.single(n, cin - c1, c1, edge, cout, None, split_ok, materialised=True)
+            if route == 'e2':
                 y = ops.conv3d_e2_split_gn_relu(x, aff, ops.pack_conv3_e2_split_weight(w, edge), cout)
-            elif edge == 1:
+            elif route == 'direct':
                 y = ops.conv3d_gn_relu(x, None, aff, None, cout, direct_weight=w)
-            elif split_ok and ops.conv_split_supported(x, None, cout):
+            elif route == 'split_box':
                 y = ops.conv3d_split_gn_relu(x, aff, ops.pack_conv3_split_weight(w), cout)
-            elif split_ok and low is not None and ops.conv_up_split_supported(skip, low, cout):
-                y = ops.conv3d_up_split_gn_relu(skip, low, aff, ops.pack_conv3_up_split_weight(w, cin - low.shape[1]), cout)
+            elif route == 'up_split':
+                y = ops.conv3d_up_split_gn_relu(skip, low, aff, ops.pack_conv3_up_split_weight(w, cin - c1), cout)
             else:
                 y = ops.conv3d_gn_relu(x, None, aff, ops.pack_conv3_weight(w), cout)
         ctx.save_for_backward(x, gamma, weight, aff, y)
@@ -175,8 +172,6 @@ class ConvGnRelu(torch.autograd.Function):
                 dz = relu_backward(dy.contiguous(), y) if y.numel() % 4 == 0 else dy * (y > 0)
             if use_dgrad:
                 dxn, inv_s = dgrad_split(dz, ident, weight, cin), scales[1:]
-            if inv_s is not None:
-                pass
             elif edge >= 2:
                 wt = weight.flip(2, 3, 4).transpose(0, 1).contiguous()          # [cin, cout, 3,3,3]: the data-gradient conv's weight
                 ident = torch.zeros((n, cout, 4), dtype=torch.float32, device=x.device)

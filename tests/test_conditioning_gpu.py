@@ -377,7 +377,7 @@ def test_presplit_level0_double_conv(ops):
             ops.USE_PRESPLIT = saved
 
     with torch.no_grad():
-        assert blk._presplit_ok(x)
+        assert blk.route(x, pool='also') == 'cin1_presplit'
     fast, plain = run(True), run(False)
     idx, sub = subset(n, fams)
     ref = two_layers64(src[idx].double(), (blk.SingleConv1, blk.SingleConv2))
@@ -407,7 +407,7 @@ def test_presplit_prepooled_handover(ops):
         zero_first_group(blk.SingleConv1, blk.SingleConv2.groupnorm)
     src, fams = cnd.mixed(gen, n, 1, 16, 8)
     with torch.no_grad():
-        assert e1.basic_module.accepts_prepooled(n, 16, 8)
+        assert e0.basic_module.route(dev(src), pool='only', next_block=e1.basic_module) == 'cin1_presplit_handed' and e1.basic_module.accepts_prepooled(n, 16, 8)
         outs = {}
         try:
             for flag in (True, False):
@@ -435,7 +435,6 @@ def test_presplit_prepooled_handover(ops):
 def test_presplit_decoder_pair(ops, n):
     """as test_presplit_route_of_a_decoder_conv_pair: StepDownDoubleConv 32 + 64 -> 56 -> 16 @8^3"""
     from model.unet import StepDownDoubleConv
-    from model import unet as unet_mod
     c0, c1, cmid, cout = 32, 64, 56, 16
     torch.manual_seed(n)
     blk = StepDownDoubleConv(c0 + c1, cout, encoder=False, num_groups=8).to(DEV).eval()
@@ -445,7 +444,7 @@ def test_presplit_decoder_pair(ops, n):
     zero_first_group(blk.SingleConv1, blk.SingleConv2.groupnorm)
     skip, low, fams = cnd.mixed_pair(gen, n, c0, c1, 8, 8)
     with torch.no_grad():
-        assert unet_mod._decoder_pair_presplit_ok(blk.SingleConv1, blk.SingleConv2, dev(skip), dev(low))
+        assert blk.route(dev(skip), dev(low)) == ('decoder_presplit_pm' if n >= 2048 else 'decoder_presplit')
         assert ops.conv_up_split_presplit_pm_supported(dev(skip), dev(low), cmid, 8, cout) == (n >= 2048)
         got = blk(dev(skip), dev(low))
         try:
@@ -521,7 +520,7 @@ def test_presplit_encoder_pair(ops, n):
     src, fams = cnd.mixed(gen, n, 16, 8, 8)
     x = dev(src)
     with torch.no_grad():
-        assert blk._box_pair_presplit_ok(x)
+        assert all(blk.route(x, pool=pool) == 'box_presplit' for pool in (None, 'also', 'only'))
         outs = {}
         try:
             for flag in (True, False):

@@ -1342,7 +1342,7 @@ def test_presplit_route_of_a_level0_double_conv(ops, n, pool):
             ops.USE_PRESPLIT = saved
 
     with torch.no_grad():
-        assert blk._presplit_ok(x)
+        assert blk.route(x, pool=pool) == 'cin1_presplit'
     fast, plain = run(True), run(False)
     fast = fast if isinstance(fast, tuple) else (fast,)
     plain = plain if isinstance(plain, tuple) else (plain,)
@@ -1382,7 +1382,7 @@ def test_prepooled_handover_between_the_first_two_levels(ops):
     x = rnd(gen, 2100, 1, 16, 16, 16)
     e0, e1 = net.encoders[0], net.encoders[1]
     with torch.no_grad():
-        assert e1.basic_module.accepts_prepooled(2100, 16, 8)
+        assert e0.basic_module.route(x.to(DEV), pool='only', next_block=e1.basic_module) == 'cin1_presplit_handed' and e1.basic_module.accepts_prepooled(2100, 16, 8)
         outs = {}
         for flag in (True, False):
             ops.USE_PREPOOL = flag
@@ -1422,8 +1422,7 @@ def test_presplit_route_of_a_decoder_conv_pair(ops, shape):
     gen = torch.Generator().manual_seed(3)
     skip, low = rnd(gen, n, c0, 8, 8, 8).relu_(), rnd(gen, n, c1, 4, 4, 4).relu_()
     with torch.no_grad():
-        from model import unet as unet_mod
-        assert unet_mod._decoder_pair_presplit_ok(blk.SingleConv1, blk.SingleConv2, skip.to(DEV), low.to(DEV))
+        assert blk.route(skip.to(DEV), low.to(DEV)) == ('decoder_presplit_pm' if n >= 2048 else 'decoder_presplit')
         got = blk(skip.to(DEV), low.to(DEV))
         ops.USE_PRESPLIT = False
         plain = blk(skip.to(DEV), low.to(DEV))
@@ -1495,7 +1494,7 @@ def test_presplit_route_of_an_encoder_pair_on_whole_samples(ops, n):
     gen = torch.Generator().manual_seed(4)
     x = rnd(gen, n, 16, 8, 8, 8).relu_()                            # 2070: the producer on the persistent z-column form (k_conv3_split_zcm, pre-split epilogue)
     with torch.no_grad():
-        assert blk._box_pair_presplit_ok(x.to(DEV))
+        assert all(blk.route(x.to(DEV), pool=pool) == 'box_presplit' for pool in (None, 'also', 'only'))
         outs = {}
         for flag in (True, False):
             ops.USE_PRESPLIT = flag
