@@ -131,6 +131,9 @@ class AttentionBlock(nn.Module):
         b = x.shape[0]
         x_feat = self.theta(x.contiguous()).reshape((b, -1))
         p_feat = self.phi(p.contiguous()).reshape((b, -1))
+        if ops.needs_grad(x_feat, p_feat):
+            # grad mode: the encoders' outputs are saved by autograd, so nothing is written into them, and the normalisation has its backward
+            return nn.functional.normalize(x_feat, dim=1), nn.functional.normalize(p_feat, dim=1)
         return ops.l2_normalize_rows_(x_feat), ops.l2_normalize_rows_(p_feat)
 
     def _forward_autograd(self, x, p, gumbel_noise):

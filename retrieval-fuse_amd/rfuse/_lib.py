@@ -1,5 +1,5 @@
-"""ctypes binding of librfuse_hip.so (the C ABI declared in include/rfuse.h, the evaluation ABI of include/rfuse_eval.h and the training-loss ABI
-of include/rfuse_train.h).
+"""ctypes binding of librfuse_hip.so (the C ABI declared in include/rfuse.h, the evaluation ABI of include/rfuse_eval.h, the training-loss ABI
+of include/rfuse_train.h and the contrastive-loss ABI of include/rfuse_contrastive.h).
 
 The argument and return types are read from the header itself at import (``parse_header``): there is no second copy of the ABI to keep
 in step.  There is NO fallback: if the library is missing a RuntimeError is raised, and every entry point that returns a status
@@ -8,7 +8,8 @@ first so that the HIP runtime the library binds to is the one PyTorch-ROCm alrea
 
 ``load()`` binds include/rfuse.h (``SIGNATURES``; the profiling wrapper brackets these); ``load_eval()`` binds include/rfuse_eval.h
 (``EVAL_SIGNATURES``: the mesh metrics, rfuse/mesh_metrics.py) and ``load_train()`` include/rfuse_train.h (``TRAIN_SIGNATURES``: the shape loss,
-rfuse/losses.py), both from the same shared object, under the same status rule.
+rfuse/losses.py) and ``load_contrastive()`` include/rfuse_contrastive.h (``CONTRASTIVE_SIGNATURES``: NT-Xent and the sliced attention contrastive
+loss, rfuse/losses.py), all from the same shared object, under the same status rule.
 """
 import ctypes
 import os
@@ -22,6 +23,7 @@ LIB_PATH = Path(os.environ.get('RFUSE_LIB', _HERE / 'librfuse_hip.so'))
 HEADER_PATH = _HERE.parents[1] / 'include' / 'rfuse.h'
 EVAL_HEADER_PATH = _HERE.parents[1] / 'include' / 'rfuse_eval.h'
 TRAIN_HEADER_PATH = _HERE.parents[1] / 'include' / 'rfuse_train.h'
+CONTRASTIVE_HEADER_PATH = _HERE.parents[1] / 'include' / 'rfuse_contrastive.h'
 
 # every scalar type include/rfuse.h uses; any pointer is a c_void_p, and `const char*` as a return type a c_char_p
 _SCALARS = {'int': ctypes.c_int, 'float': ctypes.c_float, 'size_t': ctypes.c_size_t, 'int64_t': ctypes.c_int64, 'long long': ctypes.c_int64}
@@ -71,6 +73,7 @@ def parse_header(text):
 SIGNATURES = parse_header(HEADER_PATH.read_text())
 EVAL_SIGNATURES = parse_header(EVAL_HEADER_PATH.read_text())
 TRAIN_SIGNATURES = parse_header(TRAIN_HEADER_PATH.read_text())
+CONTRASTIVE_SIGNATURES = parse_header(CONTRASTIVE_HEADER_PATH.read_text())
 
 
 def is_status(name, table=None):
@@ -88,6 +91,7 @@ def _raise_on_status(rc, fn, args):
 _lib = None
 _eval = None
 _train = None
+_contrastive = None
 
 
 class _Library:
@@ -157,6 +161,14 @@ def load_train():
     if _train is None:
         _train = _Library(load()._cdll, TRAIN_SIGNATURES)
     return _train
+
+
+def load_contrastive():
+    """The entry points of include/rfuse_contrastive.h, bound like ``load_eval()``'s."""
+    global _contrastive
+    if _contrastive is None:
+        _contrastive = _Library(load()._cdll, CONTRASTIVE_SIGNATURES)
+    return _contrastive
 
 
 def check(rc, what):

@@ -1,4 +1,4 @@
-"""The shape loss of the reference's refinement trainer on the device: ``RefinementTrainingModule.augment_batch_data`` / ``loss_shape`` /
+"""The losses of the reference's refinement trainer on the device.  First the shape loss: ``RefinementTrainingModule.augment_batch_data`` / ``loss_shape`` /
 ``adjust_weights`` (trainer/train_refinement.py:175-183, :231-253), ``PatchedSceneDataset.compute_normals`` (dataset/patched_scene_dataset.py:139-146)
 and ``get_cosine_similarity`` (model/loss.py:78-85), in csrc/shape_loss.hip behind include/rfuse_train.h.  NO CPU fallback.
 
@@ -14,6 +14,17 @@ the same input return the same bits (float64 partial sums combined in a fixed or
 What differs from the reference's float32 evaluation is rounding only: the 27 Sobel taps are accumulated exactly and rounded once (a flat neighbourhood
 gives a gradient of exactly 0, on which the valid mask ``|n| != 0`` rests, independent of any summation order), the sums of the two means are float64, and
 the gradient is the analytic ``d cos / d g = (t^ - g^ (g^ . t^)) / |g|`` evaluated in float64 instead of autograd through three normalisations.
+
+Then the contrastive term (csrc/ntxent.hip behind include/rfuse_contrastive.h), also without a CPU fallback:
+
+    ntx = NTXent(temperature, use_cosine_similarity=True, sig_scale=80, sig_shift=-65)      # model/loss.py NTXentLoss, one group
+    loss = ntx(zis, zjs, iou_matrix=None)                                                    # () float32
+    acl = AttnContrastiveLoss(temperature=0.05, max_rows=1280)                               # trainer :208-221 compute_sliced_attn_nt_xent_loss
+    loss = acl(num_slices, x_attn_fpred, x_attn_ftgt, occupancy_attn)                        # (1,) float32; acl.last_counts int64 [3] on the device
+
+The reference's sliced loss asks the host twice per slice whether and how many rows are occupied, boolean-indexes them and runs NTXentLoss on each slice in
+turn.  Here the selection is made on the device (the same greedy rule in slice order), the similarity matrix is never materialised, and nothing waits for the
+host: four launches forward, one backward.  The arithmetic is float64 from the float32 features on, the sums have one order: the same bits on every call.
 """
 import torch
 
@@ -152,3 +163,110 @@ class ShapeLoss:
         if not self.loss_normal > 0:
             normal, total = normal.detach().reshape(1), total.reshape(1)
         return total, l1, normal
+
+
+# ------------------------------------------------------------------------------------------------ the contrastive loss
+_NTX_SLICES, _NTX_GROUP, _NTX_DIM = 4096, 4096, 256      # the supported range of include/rfuse_contrastive.h
+
+
+def _features(t, what):
+    if not isinstance(t, torch.Tensor):
+        raise TypeError('%s: expected a torch.Tensor' % what)
+    if not t.is_cuda:
+        raise RuntimeError('%s: the contrastive loss runs on the GPU only (got a %s tensor); there is no CPU fallback' % (what, t.device))
+    if t.dim() != 2 or t.numel() == 0:
+        raise ValueError('%s: expected a non-empty [rows, features] tensor, got %s' % (what, tuple(t.shape)))
+    if t.dtype != torch.float32:
+        raise TypeError('%s: expected torch.float32, got %s' % (what, t.dtype))
+    return t.contiguous()
+
+
+@_device_scoped
+def _ntx_forward(zis, zjs, occ, iou, num_slices, max_rows, cosine, tau, sig_scale, sig_shift):
+    n_rows, dim = zis.shape
+    lib = _lib.load_contrastive()
+    dev = zis.device
+    nbytes = int(lib.rf_ntx_ws_bytes(n_rows, num_slices, max_rows, dim))
+    if nbytes == 0:
+        raise ValueError('contrastive loss: %d rows of %d features in %d slices, at most %d rows, is outside the supported range (1 <= features <= %d, '
+                         'slices <= %d, 1 <= min(rows // slices, max_rows) <= %d)' % (n_rows, dim, num_slices, max_rows, _NTX_DIM, _NTX_SLICES, _NTX_GROUP))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    counts = torch.empty(3, dtype=torch.int64, device=dev)
+    lib.rf_ntx_plan(_p(occ), n_rows, num_slices, max_rows, dim, _p(ws), nbytes, _p(counts), _stream())
+    lib.rf_ntx_forward(_p(zis), _p(zjs), _p(iou), n_rows, num_slices, max_rows, dim, cosine, tau, sig_scale, sig_shift, _p(ws), nbytes, _p(loss), _stream())
+    return loss, counts, ws
+
+
+@_device_scoped
+def _ntx_backward(g, iou, ws, shape, num_slices, max_rows, cosine, tau, sig_scale, sig_shift):
+    n_rows, dim = shape
+    dzis = torch.empty(shape, dtype=torch.float32, device=g.device)
+    dzjs = torch.empty(shape, dtype=torch.float32, device=g.device)
+    _lib.load_contrastive().rf_ntx_backward(_p(iou), _p(g), n_rows, num_slices, max_rows, dim, cosine, tau, sig_scale, sig_shift, _p(ws), ws.numel(), _p(dzis),
+                                            _p(dzjs), _stream())
+    return dzis, dzjs
+
+
+class _NTXentFn(torch.autograd.Function):
+    """(zis, zjs; occupancy, iou, constants) -> (float32 [1], counts); the gradient goes to the two feature tensors only"""
+
+    @staticmethod
+    def forward(ctx, zis, zjs, occ, iou, num_slices, max_rows, cosine, tau, sig_scale, sig_shift):
+        loss, counts, ws = _ntx_forward(zis, zjs, occ, iou, num_slices, max_rows, cosine, tau, sig_scale, sig_shift)
+        if any(ctx.needs_input_grad[:2]):
+            ctx.save_for_backward(ws, iou) if iou is not None else ctx.save_for_backward(ws)
+        ctx.consts = (tuple(zis.shape), num_slices, max_rows, cosine, tau, sig_scale, sig_shift)
+        ctx.mark_non_differentiable(counts)
+        return loss, counts
+
+    @staticmethod
+    def backward(ctx, g_loss, _g_counts):
+        ws, iou = (tuple(ctx.saved_tensors) + (None,))[:2]
+        dzis, dzjs = _ntx_backward(g_loss.to(torch.float32).contiguous(), iou, ws, *ctx.consts)
+        return (dzis, dzjs) + (None,) * 8
+
+
+class NTXent:
+    """One ``model.loss.NTXentLoss`` call on the device: ``zis``, ``zjs`` float32 [B, dim] (1 <= B <= 4096, dim <= 256), optionally the [2B, 2B] IoU matrix of
+    the retrieval trainer's ``iou_scaling`` (rows and columns in the order [zjs; zis]).  Returns the scalar () float32."""
+
+    def __init__(self, temperature, use_cosine_similarity=True, sig_scale=80, sig_shift=-65):
+        self.temperature, self.use_cosine_similarity, self.sig_scale, self.sig_shift = temperature, bool(use_cosine_similarity), sig_scale, sig_shift
+
+    def __call__(self, zis, zjs, iou_matrix=None):
+        zis, zjs = _features(zis, 'NTXent: zis'), _features(zjs, 'NTXent: zjs')
+        if zis.shape != zjs.shape:
+            raise ValueError('NTXent: zis is %s, zjs %s' % (tuple(zis.shape), tuple(zjs.shape)))
+        b = zis.shape[0]
+        if iou_matrix is not None:
+            iou_matrix = _features(iou_matrix.detach(), 'NTXent: iou_matrix')
+            if iou_matrix.shape != (2 * b, 2 * b):
+                raise ValueError('NTXent: iou_matrix is %s, expected %s' % (tuple(iou_matrix.shape), (2 * b, 2 * b)))
+        loss, _ = _NTXentFn.apply(zis, zjs, None, iou_matrix, 1, b, int(self.use_cosine_similarity), _f32(self.temperature), _f32(self.sig_scale),
+                                  _f32(self.sig_shift))
+        return loss.reshape(())
+
+
+class AttnContrastiveLoss:
+    """``RefinementTrainingModule.compute_sliced_attn_nt_xent_loss`` (trainer :208-221) with its ``NTXentLoss(temperature, True)``: the rows of the two feature
+    tensors [N, dim] in ``num_slices`` slices of N // num_slices rows, the rows with ``occupancy_attn > 0`` of a slice one NT-Xent group, slices taken in order
+    while the selected rows stay within ``max_rows``; the sum of the groups' losses, shape (1,).  ``last_counts``: int64 [3] on the device = occupied rows over
+    all slices (the trainer's ``attn_occupancy``), selected rows, selected groups.  Nothing waits for the host."""
+
+    def __init__(self, temperature=0.05, max_rows=1280):
+        self.temperature, self.max_rows = temperature, int(max_rows)
+        self.last_counts = None
+
+    def __call__(self, num_slices, x_attn_fpred, x_attn_ftgt, occupancy_attn):
+        zis, zjs = _features(x_attn_fpred, 'AttnContrastiveLoss: x_attn_fpred'), _features(x_attn_ftgt, 'AttnContrastiveLoss: x_attn_ftgt')
+        if zis.shape != zjs.shape:
+            raise ValueError('AttnContrastiveLoss: x_attn_fpred is %s, x_attn_ftgt %s' % (tuple(zis.shape), tuple(zjs.shape)))
+        if not isinstance(occupancy_attn, torch.Tensor) or not occupancy_attn.is_cuda:
+            raise RuntimeError('AttnContrastiveLoss: occupancy_attn must be a GPU tensor; there is no CPU fallback')
+        if occupancy_attn.numel() != zis.shape[0]:
+            raise ValueError('AttnContrastiveLoss: occupancy_attn has %d entries for %d rows' % (occupancy_attn.numel(), zis.shape[0]))
+        occ = (occupancy_attn.detach().reshape(-1) > 0).contiguous()          # bool: one byte per row, 0 / 1
+        loss, counts = _NTXentFn.apply(zis, zjs, occ, None, int(num_slices), self.max_rows, 1, _f32(self.temperature), 0.0, 0.0)
+        self.last_counts = counts
+        return loss
