@@ -89,7 +89,7 @@ def build(force=False, verbose=False, out=None, extra_flags=(), objdir=None):
     OUT = Path(out) if out is not None else globals()['OUT']
     objdir = Path(objdir) if objdir is not None else HERE / 'build'
     objdir.mkdir(exist_ok=True, parents=True)
-    headers = [HERE / 'common.h', HERE / 'conv_box.h', HERE / 'conv_split_common.h', HERE / 'split_operand.h', HERE / 'attn_row.h', HERE / 'philox.h',
+    headers = [HERE / 'common.h', HERE / 'conv_box.h', HERE / 'conv_split_common.h', HERE / 'conv_split_args.h', HERE / 'split_operand.h', HERE / 'attn_row.h', HERE / 'philox.h',
                HERE.parents[1] / 'include' / 'rfuse.h', HERE.parents[1] / 'include' / 'rfuse_eval.h', HERE.parents[1] / 'include' / 'rfuse_train.h',
                HERE.parents[1] / 'include' / 'rfuse_contrastive.h']
 

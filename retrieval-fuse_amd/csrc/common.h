@@ -44,6 +44,19 @@ struct RfLdsOptIn {
     }
 };
 
+// The tail of a launcher: opt in where the kernel instantiation KERN ever asks for more than the 64 KB of dynamic LDS a kernel gets without asking
+// (`lds_limit` = the most it asks for; `lds` = this launch's), launch, check.  `who`: the entry point the caller serves, for the error texts.
+template <auto KERN, class... Args>
+static inline int rf_launch(const char* who, dim3 grid, size_t lds, size_t lds_limit, hipStream_t stream, Args... args) {
+    if (lds_limit > 64 * 1024) {
+        static RfLdsOptIn opt;
+        if (int rc = opt.ensure(reinterpret_cast<const void*>(KERN), (int)lds_limit, who)) return rc;
+    }
+    hipLaunchKernelGGL(KERN, grid, dim3(512), lds, stream, args...);
+    RF_CHECK_LAUNCH(who);
+    return RF_OK;
+}
+
 static inline bool rf_is_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
 static inline int rf_ilog2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
 static inline int rf_round_up(int v, int m) { return (v + m - 1) / m * m; }

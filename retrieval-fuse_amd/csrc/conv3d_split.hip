@@ -14,10 +14,10 @@
 // before the MFMAs of the current chunk and normalised + split + written to the other buffer after them; one barrier per chunk.
 // B operands (weights): f16 fragment image from rf_conv3_split_pack_weight ([chunk][k-step][n-block][h|l][lane][8 halves]), L2-resident,
 // global -> VGPR one k-step ahead.  Register use is small (NB 1: 32 accumulator VGPRs), two workgroups per CU.
-// Pre-split output (whole 8^3 samples): the hand-over epilogue of conv_split_common.h; the triple from the sums is common.h:rf_gn_triple.
+// Pre-split output (whole 8^3 samples): the hand-over epilogue of conv_split_common.h; the triple from the sums is common.h:rf_gn_triple.  The staging
+// step is that header's too (rf_stage8 / rf_norm_split8 / rf_store_hl).  Host side: conv_split_args.h builds every entry point's ConvArgs / SplitPreOut.
 #include "common.h"
-#include "conv_box.h"
-#include "conv_split_common.h"
+#include "conv_split_args.h"
 #include <type_traits>
 
 // conv3d_split_zc.hip: the persistent z-column forms.  zc: the one-chunk pre-split layer on 16^3 samples (8 -> 16: level 0 of the retrieval backbone);
@@ -135,6 +135,7 @@ __global__ __launch_bounds__(512, WPS) void k_conv3_split(ConvArgs a, SplitPreOu
                 h = vin[r] ? st.ph[r] : zero;
                 l = vin[r] ? st.pl[r] : zero;
             } else {
+                // rf_norm_split8 written out: through it the PADC instances come out with one more s_nop / s_waitcnt and <2, 2, false, true> measured 0.5 % slower in every round
                 float y[8];
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
@@ -143,11 +144,7 @@ __global__ __launch_bounds__(512, WPS) void k_conv3_split(ConvArgs a, SplitPreOu
                 }
                 rf_split8(y, h, l);
             }
-            if (r == 0 || tid < CS_VOX - 512) {
-                unsigned char* p = lds + buf * CS_BUF + vslot[r];
-                *reinterpret_cast<h8*>(p) = h;
-                *reinterpret_cast<h8*>(p + CS_PLANE) = l;
-            }
+            if (r == 0 || tid < CS_VOX - 512) rf_store_hl(lds + buf * CS_BUF + vslot[r], CS_PLANE, h, l);
         }
     };
     // the first chunk's voxels are requested now and staged after the addressing set-up and the first weight fragments are under way
@@ -276,11 +273,7 @@ __global__ __launch_bounds__(512, WPS) void k_conv3_split(ConvArgs a, SplitPreOu
             }
 #pragma unroll
             for (int r = 0; r < 2; ++r)
-                if (r == 0 || tid < CS_VOX - 512) {
-                    unsigned char* p = lds + ((ca + 1) & 1) * CS_BUF + vslot[r];
-                    *reinterpret_cast<h8*>(p) = hq[r];
-                    *reinterpret_cast<h8*>(p + CS_PLANE) = lq[r];
-                }
+                if (r == 0 || tid < CS_VOX - 512) rf_store_hl(lds + ((ca + 1) & 1) * CS_BUF + vslot[r], CS_PLANE, hq[r], lq[r]);
         }
         __syncthreads();
     };
@@ -403,16 +396,7 @@ __global__ __launch_bounds__(512, NB == 1 ? 4 : 2) void k_conv3_split_s4(ConvArg
         for (int j = 0; j < 8; ++j) x[j] = s0[(size_t)(ca * 8 + j) * 64];
     };
     auto stage_store = [&](const float (&x)[8], int ca) {
-        float y[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const float4 af = aff[ca * 8 + j];                      // wave-uniform: scalar loads
-            y[j] = fmaf(x[j] - af.x, af.y, af.z);
-        }
-        h8 h, l;
-        rf_split8(y, h, l);
-        *reinterpret_cast<h8*>(myslot) = h;
-        *reinterpret_cast<h8*>(myslot + S4_PLANE) = l;
+        rf_stage8(myslot, S4_PLANE, x, [&](int j) { return aff[ca * 8 + j]; });      // wave-uniform triples: scalar loads
     };
 
     float xr[8];
@@ -682,19 +666,13 @@ extern "C" int rf_conv3d_split_supported(int c0, int c1, int n, int edge, int co
 }
 
 template <int NB, int WPS, bool ONE, bool PADC = false, bool PRE = false>
-static int launch_split(const ConvArgs& a, hipStream_t stream, const SplitPreOut& po = SplitPreOut{nullptr, nullptr, nullptr, 0, 0.f, nullptr, nullptr, nullptr, 0.f, 0.f}) {
-    auto kern = k_conv3_split<NB, WPS, ONE, PADC, PRE>;
-    if constexpr (!ONE) {                                             // two chunk buffers: 66,560 bytes, past the 64 KB a kernel gets without asking
-        static RfLdsOptIn opt;
-        if (int rc = opt.ensure(reinterpret_cast<const void*>(kern), CS_LDS_BYTES, "rf_conv3d_split_k3_gn_relu")) return rc;
-    }
+static int launch_split(const ConvArgs& a, hipStream_t stream, const char* who, const SplitPreOut& po = SplitPreOut{}) {
+    constexpr int LDS = ONE ? CS_BUF : CS_LDS_BYTES;                  // two chunk buffers: 66,560 bytes, past the 64 KB a kernel gets without asking
     const unsigned gx = (unsigned)a.n * (a.edge / 8) * (a.edge / 8) * (a.edge / 8);
-    hipLaunchKernelGGL(kern, dim3(gx, (unsigned)(a.cout16 / (NB * 16))), dim3(512), ONE ? CS_BUF : CS_LDS_BYTES, stream, a, po);
-    RF_CHECK_LAUNCH("rf_conv3d_split_k3_gn_relu");
-    return RF_OK;
+    return rf_launch<k_conv3_split<NB, WPS, ONE, PADC, PRE>>(who, dim3(gx, (unsigned)(a.cout16 / (NB * 16))), LDS, LDS, stream, a, po);
 }
 
-static int split_run(const ConvArgs& a, void* stream) {
+static int split_run(const ConvArgs& a, hipStream_t stream, const char* who) {
     // 32 couts: one workgroup with two n-blocks per box (158 VGPRs: every A operand read from LDS feeds six MFMAs instead of three -- the
     // 16-cout instance asks the LDS for 170 B/clk of A operands and gets 128).  Round 2 ran 32 couts as two 16-cout workgroups because this
     // instance leaves room for other kernels' waves on its SIMDs and fp32 kernels of another stream then returned different bits beside its
@@ -704,44 +682,36 @@ static int split_run(const ConvArgs& a, void* stream) {
     // a third box in flight per CU is worth 13 % (1.60 -> 1.40 ms)
     const int cin = a.c0, n = a.n, edge = a.edge;
     if (edge == 4) {
-        RF_REQUIRE(!a.pool_out, RF_E_UNSUPPORTED, "rf_conv3d_split_k3_gn_relu: the 4^3 form has no fused max-pool (pool its output with rf_maxpool3d_2_stats)");
+        RF_REQUIRE(!a.pool_out, RF_E_UNSUPPORTED, "%s: the 4^3 form has no fused max-pool (pool its output with rf_maxpool3d_2_stats)", who);
         // all couts of a 32 / 64-cout layer in one workgroup (samples staged once; 4^3 levels of the retrieval backbone: 32 -> 32, 32 -> 64, 64 -> 64)
+        static_assert(S4_LDS_BYTES <= 64 * 1024, "k_conv3_split_s4 is launched without an LDS opt-in");
         const unsigned gx = (unsigned)((n + 7) / 8), nbt = (unsigned)(a.cout16 / 16);
-        if (nbt % 4 == 0) hipLaunchKernelGGL(k_conv3_split_s4<4>, dim3(gx, nbt / 4), dim3(512), S4_LDS_BYTES, (hipStream_t)stream, a);
-        else if (nbt % 3 == 0) hipLaunchKernelGGL(k_conv3_split_s4<3>, dim3(gx, nbt / 3), dim3(512), S4_LDS_BYTES, (hipStream_t)stream, a);      // nf = 12: 48 / 96 couts
-        else if (nbt % 2 == 0) hipLaunchKernelGGL(k_conv3_split_s4<2>, dim3(gx, nbt / 2), dim3(512), S4_LDS_BYTES, (hipStream_t)stream, a);
-        else hipLaunchKernelGGL(k_conv3_split_s4<1>, dim3(gx, nbt), dim3(512), S4_LDS_BYTES, (hipStream_t)stream, a);
-        RF_CHECK_LAUNCH("rf_conv3d_split_k3_gn_relu");
-        return RF_OK;
+        if (nbt % 4 == 0) return rf_launch<k_conv3_split_s4<4>>(who, dim3(gx, nbt / 4), S4_LDS_BYTES, S4_LDS_BYTES, stream, a);
+        if (nbt % 3 == 0) return rf_launch<k_conv3_split_s4<3>>(who, dim3(gx, nbt / 3), S4_LDS_BYTES, S4_LDS_BYTES, stream, a);      // nf = 12: 48 / 96 couts
+        if (nbt % 2 == 0) return rf_launch<k_conv3_split_s4<2>>(who, dim3(gx, nbt / 2), S4_LDS_BYTES, S4_LDS_BYTES, stream, a);
+        return rf_launch<k_conv3_split_s4<1>>(who, dim3(gx, nbt), S4_LDS_BYTES, S4_LDS_BYTES, stream, a);
     }
-    if (a.cout16 <= 32 && rf_split_zcm_takes(cin, n, edge, a.cout))
-        return rf_split_zcm_launch(a, SplitPreOut{nullptr, nullptr, nullptr, 0, 0.f, nullptr, nullptr, nullptr, 0.f, 0.f}, false, (hipStream_t)stream, "rf_conv3d_split_k3_gn_relu");
+    if (a.cout16 <= 32 && rf_split_zcm_takes(cin, n, edge, a.cout)) return rf_split_zcm_launch(a, SplitPreOut{}, false, stream, who);
     if (cin % 8) {
-        if (cin < 8) return launch_split<1, 6, true, true>(a, (hipStream_t)stream);                   // 6 -> 12 of the nf = 12 U-Nets: one chunk, two zero slots
-        if (a.cout16 % 32 == 0) return launch_split<2, 2, false, true>(a, (hipStream_t)stream);
-        return launch_split<1, 4, false, true>(a, (hipStream_t)stream);
+        if (cin < 8) return launch_split<1, 6, true, true>(a, stream, who);                           // 6 -> 12 of the nf = 12 U-Nets: one chunk, two zero slots
+        if (a.cout16 % 32 == 0) return launch_split<2, 2, false, true>(a, stream, who);
+        return launch_split<1, 4, false, true>(a, stream, who);
     }
-    if (cin > 8 && a.cout16 % 32 == 0) return launch_split<2, 2, false>(a, (hipStream_t)stream);
-    return cin == 8 ? launch_split<1, 6, true>(a, (hipStream_t)stream) : launch_split<1, 4, false>(a, (hipStream_t)stream);
+    if (cin > 8 && a.cout16 % 32 == 0) return launch_split<2, 2, false>(a, stream, who);
+    return cin == 8 ? launch_split<1, 6, true>(a, stream, who) : launch_split<1, 4, false>(a, stream, who);
 }
 
+// Every entry point below: the supported check, the pointer check, the arguments (conv_split_args.h), the dispatch.
 extern "C" int rf_conv3d_split_k3_gn_relu(const float* src, int cin, int n, int edge, const float* gn_affine, const void* w_packed, int cout,
                                            float* out, double* stats, float* pool_out, double* pool_stats, void* stream) {
+    const char* who = "rf_conv3d_split_k3_gn_relu";
     RF_REQUIRE(rf_conv3d_split_supported(cin, 0, n, edge, cout), RF_E_UNSUPPORTED,
                "rf_conv3d_split_k3_gn_relu: takes cin >= 6 (at least 3/4 of the next multiple of 8), up to 192 couts, edge >= 8 and enough 8^3 boxes (got cin=%d n=%d edge=%d cout=%d)",
                cin, n, edge, cout);
-    RF_REQUIRE(src && gn_affine && w_packed && (out || pool_out), RF_E_INVALID, "rf_conv3d_split_k3_gn_relu: null pointer");
-    RF_REQUIRE(out || !stats, RF_E_INVALID, "rf_conv3d_split_k3_gn_relu: statistics of an output that is not written");
-    RF_REQUIRE(pool_out || !pool_stats, RF_E_INVALID, "rf_conv3d_split_k3_gn_relu: pooled statistics without a pooled output");
-    ConvArgs a;
-    a.src0 = src; a.src1 = nullptr; a.affine = reinterpret_cast<const float4*>(gn_affine); a.wp = reinterpret_cast<const float*>(w_packed); a.out = out;
-    a.c0 = cin; a.c1 = 0; a.n = n; a.edge = edge; a.cout = cout; a.cin4 = cin; a.cout16 = rf_round_up(cout, 16);
-    a.stats = reinterpret_cast<double2*>(stats);
-    a.stats_tiles = (stats || pool_stats) ? (edge == 4 ? 1 : (edge / 8) * (edge / 8) * (edge / 8)) : 0;
-    a.pool_out = pool_out; a.pool_stats = reinterpret_cast<double2*>(pool_stats);
-    a.pool_mode = pool_out ? (out ? 1 : 2) : 0;
-    a.floor = 0.f;
-    return split_run(a, stream);
+    if (int rc = split_check_pointers(who, src && gn_affine && w_packed, out, stats, pool_out, pool_stats)) return rc;
+    const int tiles = edge == 4 ? 1 : (edge / 8) * (edge / 8) * (edge / 8);
+    const ConvArgs a = split_with_outputs(split_conv_args(src, cin, n, edge, gn_affine, w_packed, cout), out, stats, pool_out, pool_stats, tiles);
+    return split_run(a, (hipStream_t)stream, who);
 }
 
 // The same conv as a plain operator for the training slice's data gradient (rfuse/autograd.py: d xn = conv3(dz, W^T with flipped taps)): any cout
@@ -755,16 +725,12 @@ extern "C" int rf_conv3d_split_k3_gn_supported(int cin, int n, int edge, int cou
 
 extern "C" int rf_conv3d_split_k3_gn(const float* src, int cin, int n, int edge, const float* gn_affine, const void* w_packed, int cout, int relu,
                                       float* out, void* stream) {
+    const char* who = "rf_conv3d_split_k3_gn";
     RF_REQUIRE(rf_conv3d_split_k3_gn_supported(cin, n, edge, cout), RF_E_UNSUPPORTED,
                "rf_conv3d_split_k3_gn: takes cin >= 6 (at least 3/4 of the next multiple of 8), edge >= 8 with enough 8^3 boxes or whole 4^3 samples (got cin=%d n=%d edge=%d cout=%d)",
                cin, n, edge, cout);
-    RF_REQUIRE(src && gn_affine && w_packed && out, RF_E_INVALID, "rf_conv3d_split_k3_gn: null pointer");
-    ConvArgs a;
-    a.src0 = src; a.src1 = nullptr; a.affine = reinterpret_cast<const float4*>(gn_affine); a.wp = reinterpret_cast<const float*>(w_packed); a.out = out;
-    a.c0 = cin; a.c1 = 0; a.n = n; a.edge = edge; a.cout = cout; a.cin4 = cin; a.cout16 = rf_round_up(cout, 16);
-    a.stats = nullptr; a.stats_tiles = 0; a.pool_out = nullptr; a.pool_stats = nullptr; a.pool_mode = 0;
-    a.floor = relu ? 0.f : -INFINITY;
-    return split_run(a, stream);
+    if (int rc = split_check_pointers(who, src && gn_affine && w_packed, out, nullptr, nullptr, nullptr)) return rc;
+    return split_run(split_with_plain_output(split_conv_args(src, cin, n, edge, gn_affine, w_packed, cout), out, relu), (hipStream_t)stream, who);
 }
 
 // The same layer on a PRE-SPLIT input (already normalised for this layer's GroupNorm and split by its producer: rf_conv3d_cin1_presplit):
@@ -772,7 +738,6 @@ extern "C" int rf_conv3d_split_k3_gn(const float* src, int cin, int n, int edge,
 extern "C" int rf_conv3d_split_pre_supported(int cin, int n, int edge, int cout) {
     return cin >= 8 && cin % 8 == 0 && edge >= 8 && rf_conv3d_split_supported(cin, 0, n, edge, cout);
 }
-
 
 // tiles per (sample, cout) of the statistics rf_conv3d_split_pre_k3_relu writes for this shape ([n][cout][tiles] double2): one per 8^3 box, or one per
 // sample where the persistent form (which sums a sample's boxes itself) takes the layer
@@ -783,27 +748,17 @@ extern "C" int rf_conv3d_split_pre_stats_tiles(int cin, int n, int edge, int cou
 
 extern "C" int rf_conv3d_split_pre_k3_relu(const void* src_presplit, int cin, int n, int edge, const void* w_packed, int cout,
                                            float* out, double* stats, float* pool_out, double* pool_stats, void* stream) {
+    const char* who = "rf_conv3d_split_pre_k3_relu";
+    const hipStream_t st = (hipStream_t)stream;
     RF_REQUIRE(rf_conv3d_split_pre_supported(cin, n, edge, cout), RF_E_UNSUPPORTED,
                "rf_conv3d_split_pre_k3_relu: takes cin in eights, up to 32 couts, edge >= 8 and enough 8^3 boxes (got cin=%d n=%d edge=%d cout=%d)", cin, n, edge, cout);
-    RF_REQUIRE(src_presplit && w_packed && (out || pool_out), RF_E_INVALID, "rf_conv3d_split_pre_k3_relu: null pointer");
-    RF_REQUIRE(out || !stats, RF_E_INVALID, "rf_conv3d_split_pre_k3_relu: statistics of an output that is not written");
-    RF_REQUIRE(pool_out || !pool_stats, RF_E_INVALID, "rf_conv3d_split_pre_k3_relu: pooled statistics without a pooled output");
-    ConvArgs a;
-    a.src0 = reinterpret_cast<const float*>(src_presplit); a.src1 = nullptr; a.affine = nullptr; a.wp = reinterpret_cast<const float*>(w_packed); a.out = out;
-    a.c0 = cin; a.c1 = 0; a.n = n; a.edge = edge; a.cout = cout; a.cin4 = cin; a.cout16 = rf_round_up(cout, 16);
-    a.stats = reinterpret_cast<double2*>(stats);
-    a.stats_tiles = (stats || pool_stats) ? (edge / 8) * (edge / 8) * (edge / 8) : 0;
-    a.pool_out = pool_out; a.pool_stats = reinterpret_cast<double2*>(pool_stats);
-    a.pool_mode = pool_out ? (out ? 1 : 2) : 0;
-    a.floor = 0.f;
-    if (rf_split_zc_takes(cin, n, edge, cout)) {
-        a.stats_tiles = 1;
-        return rf_split_zc_launch(a, SplitPreOut{nullptr, nullptr, nullptr, 0, 0.f, nullptr, nullptr, nullptr, 0.f, 0.f}, (hipStream_t)stream);
-    }
-    if (a.cout16 <= 32 && rf_split_zcm_takes(cin, n, edge, cout))
-        return rf_split_zcm_launch(a, SplitPreOut{nullptr, nullptr, nullptr, 0, 0.f, nullptr, nullptr, nullptr, 0.f, 0.f}, true, (hipStream_t)stream, "rf_conv3d_split_pre_k3_relu");
-    if (cin > 8 && a.cout16 == 32) return launch_split<2, 2, false, false, true>(a, (hipStream_t)stream);
-    return cin == 8 ? launch_split<1, 6, true, false, true>(a, (hipStream_t)stream) : launch_split<1, 4, false, false, true>(a, (hipStream_t)stream);
+    if (int rc = split_check_pointers(who, src_presplit && w_packed, out, stats, pool_out, pool_stats)) return rc;
+    const ConvArgs a = split_with_outputs(split_conv_args(src_presplit, cin, n, edge, nullptr, w_packed, cout), out, stats, pool_out, pool_stats,
+                                          rf_conv3d_split_pre_stats_tiles(cin, n, edge, cout));
+    if (rf_split_zc_takes(cin, n, edge, cout)) return rf_split_zc_launch(a, SplitPreOut{}, st);
+    if (a.cout16 <= 32 && rf_split_zcm_takes(cin, n, edge, cout)) return rf_split_zcm_launch(a, SplitPreOut{}, true, st, who);
+    if (cin > 8 && a.cout16 == 32) return launch_split<2, 2, false, false, true>(a, st, who);
+    return cin == 8 ? launch_split<1, 6, true, false, true>(a, st, who) : launch_split<1, 4, false, false, true>(a, st, who);
 }
 
 // rf_conv3d_split_pre_k3_relu on a pre-split input of whole 8^3 samples whose voxel slots are in PARITY-MAJOR order (rf_conv3d_up_split_presplit_pm): the
@@ -814,21 +769,12 @@ extern "C" int rf_conv3d_split_pre_pm_supported(int cin, int n, int edge, int co
 
 extern "C" int rf_conv3d_split_pre_pm_k3_relu(const void* src_presplit_pm, int cin, int n, int edge, const void* w_packed, int cout,
                                               float* out, double* stats, float* pool_out, double* pool_stats, void* stream) {
+    const char* who = "rf_conv3d_split_pre_pm_k3_relu";
     RF_REQUIRE(rf_conv3d_split_pre_pm_supported(cin, n, edge, cout), RF_E_UNSUPPORTED,
                "rf_conv3d_split_pre_pm_k3_relu: takes whole 8^3 samples (n >= 2048), cin >= 16 in eights, up to 32 couts (got cin=%d n=%d edge=%d cout=%d)", cin, n, edge, cout);
-    RF_REQUIRE(src_presplit_pm && w_packed && (out || pool_out), RF_E_INVALID, "rf_conv3d_split_pre_pm_k3_relu: null pointer");
-    RF_REQUIRE(out || !stats, RF_E_INVALID, "rf_conv3d_split_pre_pm_k3_relu: statistics of an output that is not written");
-    RF_REQUIRE(pool_out || !pool_stats, RF_E_INVALID, "rf_conv3d_split_pre_pm_k3_relu: pooled statistics without a pooled output");
-    ConvArgs a;
-    a.src0 = reinterpret_cast<const float*>(src_presplit_pm); a.src1 = nullptr; a.affine = nullptr; a.wp = reinterpret_cast<const float*>(w_packed); a.out = out;
-    a.c0 = cin; a.c1 = 0; a.n = n; a.edge = edge; a.cout = cout; a.cin4 = cin; a.cout16 = rf_round_up(cout, 16);
-    a.stats = reinterpret_cast<double2*>(stats);
-    a.stats_tiles = (stats || pool_stats) ? 1 : 0;
-    a.pool_out = pool_out; a.pool_stats = reinterpret_cast<double2*>(pool_stats);
-    a.pool_mode = pool_out ? (out ? 1 : 2) : 0;
-    a.floor = 0.f;
-    a.src_pm = 1;
-    return rf_split_zcm_launch(a, SplitPreOut{nullptr, nullptr, nullptr, 0, 0.f, nullptr, nullptr, nullptr, 0.f, 0.f}, true, (hipStream_t)stream, "rf_conv3d_split_pre_pm_k3_relu");
+    if (int rc = split_check_pointers(who, src_presplit_pm && w_packed, out, stats, pool_out, pool_stats)) return rc;
+    const ConvArgs a = split_from_parity_major(split_with_outputs(split_conv_args(src_presplit_pm, cin, n, edge, nullptr, w_packed, cout), out, stats, pool_out, pool_stats, 1));
+    return rf_split_zcm_launch(a, SplitPreOut{}, true, (hipStream_t)stream, who);
 }
 
 // rf_conv3d_split_k3_gn_relu on whole 8^3 samples with up to 16 couts, its output handed to the NEXT SingleConv pre-split: the workgroup holds
@@ -840,17 +786,15 @@ extern "C" int rf_conv3d_split_presplit_supported(int cin, int n, int edge, int 
 
 extern "C" int rf_conv3d_split_presplit(const float* src, int cin, int n, int edge, const float* gn_affine, const void* w_packed, int cout, const float* next_gamma,
                                         const float* next_beta, int next_groups, float eps, void* out_presplit, double* stats, void* stream) {
+    const char* who = "rf_conv3d_split_presplit";
+    const hipStream_t st = (hipStream_t)stream;
     RF_REQUIRE(rf_conv3d_split_presplit_supported(cin, n, edge, cout, next_groups), RF_E_UNSUPPORTED,
                "rf_conv3d_split_presplit: takes whole 8^3 samples, cin >= 16 in eights, 8 or 16 couts in whole groups (got cin=%d n=%d edge=%d cout=%d groups=%d)", cin, n, edge, cout, next_groups);
-    RF_REQUIRE(src && gn_affine && w_packed && next_gamma && next_beta && out_presplit, RF_E_INVALID, "rf_conv3d_split_presplit: null pointer");
-    ConvArgs a;
-    a.src0 = src; a.src1 = nullptr; a.affine = reinterpret_cast<const float4*>(gn_affine); a.wp = reinterpret_cast<const float*>(w_packed); a.out = nullptr;
-    a.c0 = cin; a.c1 = 0; a.n = n; a.edge = edge; a.cout = cout; a.cin4 = cin; a.cout16 = 16;
-    a.stats = reinterpret_cast<double2*>(stats); a.stats_tiles = stats ? 1 : 0;
-    a.pool_out = nullptr; a.pool_stats = nullptr; a.pool_mode = 0; a.floor = 0.f;
-    const SplitPreOut po{reinterpret_cast<h8*>(out_presplit), next_gamma, next_beta, next_groups, eps, nullptr, nullptr, nullptr, 0.f, 0.f};
-    if (cout <= 16 && rf_split_zcm_takes(cin, n, edge, cout)) return rf_split_zcm_launch(a, po, false, (hipStream_t)stream, "rf_conv3d_split_presplit");
-    return launch_split<1, 4, false>(a, (hipStream_t)stream, po);
+    if (int rc = split_check_pointers(who, src && gn_affine && w_packed && next_gamma && next_beta, out_presplit, nullptr, nullptr, nullptr)) return rc;
+    const ConvArgs a = split_with_handover_stats(split_conv_args(src, cin, n, edge, gn_affine, w_packed, cout), stats);
+    const SplitPreOut po = SplitPreOut::presplit(out_presplit, next_gamma, next_beta, next_groups, eps);
+    if (rf_split_zcm_takes(cin, n, edge, cout)) return rf_split_zcm_launch(a, po, false, st, who);
+    return launch_split<1, 4, false>(a, st, who, po);
 }
 
 // rf_conv3d_split_k3_gn_relu with the final decoder's head fused into the epilogue (reference model/refinement.py:48-61 + trainer/train_refinement.py:242-243):
@@ -862,16 +806,15 @@ extern "C" int rf_conv3d_split_pointwise_supported(int cin, int n, int edge, int
 
 extern "C" int rf_conv3d_split_k3_gn_relu_pointwise_tanh(const float* src, int cin, int n, int edge, const float* gn_affine, const void* w_packed, int cout,
                                                          const float* pw_w, const float* pw_b, float post_add, float post_mul, float* out1, void* stream) {
+    const char* who = "rf_conv3d_split_k3_gn_relu_pointwise_tanh";
+    const hipStream_t st = (hipStream_t)stream;
     RF_REQUIRE(rf_conv3d_split_pointwise_supported(cin, n, edge, cout), RF_E_UNSUPPORTED,
                "rf_conv3d_split_k3_gn_relu_pointwise_tanh: takes the shapes of rf_conv3d_split_k3_gn_relu with cin >= 12 and up to 16 couts (got cin=%d n=%d edge=%d cout=%d)", cin, n, edge, cout);
-    RF_REQUIRE(src && gn_affine && w_packed && pw_w && pw_b && out1, RF_E_INVALID, "rf_conv3d_split_k3_gn_relu_pointwise_tanh: null pointer");
-    ConvArgs a;
-    a.src0 = src; a.src1 = nullptr; a.affine = reinterpret_cast<const float4*>(gn_affine); a.wp = reinterpret_cast<const float*>(w_packed); a.out = nullptr;
-    a.c0 = cin; a.c1 = 0; a.n = n; a.edge = edge; a.cout = cout; a.cin4 = cin; a.cout16 = 16;
-    a.stats = nullptr; a.stats_tiles = 0; a.pool_out = nullptr; a.pool_stats = nullptr; a.pool_mode = 0; a.floor = 0.f;
-    const SplitPreOut po{nullptr, nullptr, nullptr, 0, 0.f, out1, pw_w, pw_b, post_add, post_mul};
-    if (cout <= 16 && rf_split_zcm_takes(cin, n, edge, cout)) return rf_split_zcm_launch(a, po, false, (hipStream_t)stream, "rf_conv3d_split_k3_gn_relu_pointwise_tanh");
-    return cin % 8 ? launch_split<1, 4, false, true>(a, (hipStream_t)stream, po) : launch_split<1, 4, false>(a, (hipStream_t)stream, po);
+    if (int rc = split_check_pointers(who, src && gn_affine && w_packed && pw_w && pw_b, out1, nullptr, nullptr, nullptr)) return rc;
+    const ConvArgs a = split_conv_args(src, cin, n, edge, gn_affine, w_packed, cout);
+    const SplitPreOut po = SplitPreOut::pointwise(out1, pw_w, pw_b, post_add, post_mul);
+    if (rf_split_zcm_takes(cin, n, edge, cout)) return rf_split_zcm_launch(a, po, false, st, who);
+    return cin % 8 ? launch_split<1, 4, false, true>(a, st, who, po) : launch_split<1, 4, false>(a, st, who, po);
 }
 
 // ... on the CHANNEL-INTERLEAVED output of rf_conv3d_up_split_k3_gn_relu_ch8 ([n][cin / 8][edge^3][8] fp32): same values bit for bit, the staging loads are
@@ -882,15 +825,12 @@ extern "C" int rf_conv3d_split_pointwise_ch8_supported(int cin, int n, int edge,
 
 extern "C" int rf_conv3d_split_k3_gn_relu_pointwise_tanh_ch8(const float* src_ch8, int cin, int n, int edge, const float* gn_affine, const void* w_packed, int cout,
                                                              const float* pw_w, const float* pw_b, float post_add, float post_mul, float* out1, void* stream) {
+    const char* who = "rf_conv3d_split_k3_gn_relu_pointwise_tanh_ch8";
     RF_REQUIRE(rf_conv3d_split_pointwise_ch8_supported(cin, n, edge, cout), RF_E_UNSUPPORTED,
                "rf_conv3d_split_k3_gn_relu_pointwise_tanh_ch8: takes cin in eights (>= 16), up to 16 couts, edge >= 8 and at least 2048 boxes (got cin=%d n=%d edge=%d cout=%d)", cin, n, edge, cout);
-    RF_REQUIRE(src_ch8 && gn_affine && w_packed && pw_w && pw_b && out1, RF_E_INVALID, "rf_conv3d_split_k3_gn_relu_pointwise_tanh_ch8: null pointer");
-    ConvArgs a;
-    a.src0 = src_ch8; a.src1 = nullptr; a.affine = reinterpret_cast<const float4*>(gn_affine); a.wp = reinterpret_cast<const float*>(w_packed); a.out = nullptr;
-    a.c0 = cin; a.c1 = 0; a.n = n; a.edge = edge; a.cout = cout; a.cin4 = cin; a.cout16 = 16;
-    a.stats = nullptr; a.stats_tiles = 0; a.pool_out = nullptr; a.pool_stats = nullptr; a.pool_mode = 0; a.floor = 0.f;
-    const SplitPreOut po{nullptr, nullptr, nullptr, 0, 0.f, out1, pw_w, pw_b, post_add, post_mul};
-    return rf_split_zcm_launch_ch8_pointwise(a, po, (hipStream_t)stream, "rf_conv3d_split_k3_gn_relu_pointwise_tanh_ch8");
+    if (int rc = split_check_pointers(who, src_ch8 && gn_affine && w_packed && pw_w && pw_b, out1, nullptr, nullptr, nullptr)) return rc;
+    return rf_split_zcm_launch_ch8_pointwise(split_conv_args(src_ch8, cin, n, edge, gn_affine, w_packed, cout), SplitPreOut::pointwise(out1, pw_w, pw_b, post_add, post_mul),
+                                             (hipStream_t)stream, who);
 }
 
 // rf_conv3d_split_pre_k3_relu of a level-0 second conv (pooled output only) that ALSO hands the pooled tensor to the next level's first conv pre-split: the
@@ -908,16 +848,13 @@ extern "C" size_t rf_conv3d_split_pre_pool_presplit_scratch_floats(int cout) { r
 extern "C" int rf_conv3d_split_pre_k3_relu_pool_presplit(const void* src_presplit, int cin, int n, int edge, const void* w_packed, int cout, float* pool_out,
                                                          double* pool_stats, const float* next_gamma, const float* next_beta, int next_groups, float eps,
                                                          void* out_presplit, void* stream) {
+    const char* who = "rf_conv3d_split_pre_k3_relu_pool_presplit";
     RF_REQUIRE(rf_conv3d_split_pre_pool_presplit_supported(cin, n, edge, cout, next_groups), RF_E_UNSUPPORTED,
                "rf_conv3d_split_pre_k3_relu_pool_presplit: takes 8 -> 8 or 16 channels on 16^3 samples (n >= 512) with the couts in whole groups (got cin=%d n=%d edge=%d cout=%d groups=%d)",
                cin, n, edge, cout, next_groups);
-    RF_REQUIRE(src_presplit && w_packed && pool_out && next_gamma && next_beta && out_presplit, RF_E_INVALID, "rf_conv3d_split_pre_k3_relu_pool_presplit: null pointer");
-    ConvArgs a;
-    a.src0 = reinterpret_cast<const float*>(src_presplit); a.src1 = nullptr; a.affine = nullptr; a.wp = reinterpret_cast<const float*>(w_packed); a.out = nullptr;
-    a.c0 = cin; a.c1 = 0; a.n = n; a.edge = edge; a.cout = cout; a.cin4 = cin; a.cout16 = rf_round_up(cout, 16);
-    a.stats = nullptr; a.stats_tiles = 1; a.pool_out = pool_out; a.pool_stats = reinterpret_cast<double2*>(pool_stats); a.pool_mode = 2; a.floor = 0.f;
-    const SplitPreOut po{reinterpret_cast<h8*>(out_presplit), next_gamma, next_beta, next_groups, eps, nullptr, nullptr, nullptr, 0.f, 0.f};
-    return rf_split_zc_launch(a, po, (hipStream_t)stream);
+    if (int rc = split_check_pointers(who, src_presplit && w_packed && next_gamma && next_beta && out_presplit, nullptr, nullptr, pool_out, nullptr)) return rc;
+    const ConvArgs a = split_with_outputs(split_conv_args(src_presplit, cin, n, edge, nullptr, w_packed, cout), nullptr, nullptr, pool_out, pool_stats, 1);
+    return rf_split_zc_launch(a, SplitPreOut::presplit(out_presplit, next_gamma, next_beta, next_groups, eps), (hipStream_t)stream);
 }
 
 // rf_conv3d_split_presplit on a PRE-SPLIT input: whole 8^3 samples in, whole 8^3 samples out, both as f16 pairs normalised for their consumer's GroupNorm
@@ -929,14 +866,10 @@ extern "C" int rf_conv3d_split_pre_presplit_supported(int cin, int n, int edge, 
 
 extern "C" int rf_conv3d_split_pre_presplit(const void* src_presplit, int cin, int n, int edge, const void* w_packed, int cout, const float* next_gamma,
                                             const float* next_beta, int next_groups, float eps, void* out_presplit, double* stats, void* stream) {
+    const char* who = "rf_conv3d_split_pre_presplit";
     RF_REQUIRE(rf_conv3d_split_pre_presplit_supported(cin, n, edge, cout, next_groups), RF_E_UNSUPPORTED,
                "rf_conv3d_split_pre_presplit: takes whole 8^3 samples (n >= 2048), cin >= 16 in eights, 8 or 16 couts in whole groups (got cin=%d n=%d edge=%d cout=%d groups=%d)", cin, n, edge, cout, next_groups);
-    RF_REQUIRE(src_presplit && w_packed && next_gamma && next_beta && out_presplit, RF_E_INVALID, "rf_conv3d_split_pre_presplit: null pointer");
-    ConvArgs a;
-    a.src0 = reinterpret_cast<const float*>(src_presplit); a.src1 = nullptr; a.affine = nullptr; a.wp = reinterpret_cast<const float*>(w_packed); a.out = nullptr;
-    a.c0 = cin; a.c1 = 0; a.n = n; a.edge = edge; a.cout = cout; a.cin4 = cin; a.cout16 = 16;
-    a.stats = reinterpret_cast<double2*>(stats); a.stats_tiles = stats ? 1 : 0;
-    a.pool_out = nullptr; a.pool_stats = nullptr; a.pool_mode = 0; a.floor = 0.f;
-    const SplitPreOut po{reinterpret_cast<h8*>(out_presplit), next_gamma, next_beta, next_groups, eps, nullptr, nullptr, nullptr, 0.f, 0.f};
-    return rf_split_zcm_launch(a, po, true, (hipStream_t)stream, "rf_conv3d_split_pre_presplit");
+    if (int rc = split_check_pointers(who, src_presplit && w_packed && next_gamma && next_beta, out_presplit, nullptr, nullptr, nullptr)) return rc;
+    const ConvArgs a = split_with_handover_stats(split_conv_args(src_presplit, cin, n, edge, nullptr, w_packed, cout), stats);
+    return rf_split_zcm_launch(a, SplitPreOut::presplit(out_presplit, next_gamma, next_beta, next_groups, eps), true, (hipStream_t)stream, who);
 }

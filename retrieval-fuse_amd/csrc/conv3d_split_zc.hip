@@ -15,10 +15,10 @@
 //  * x-adjacent box PAIRS share one epilogue: the pooled rows of both boxes go through an LDS tile and leave as 128-byte runs (the box kernel wrote
 //    16-byte fragments: 4.2x write amplification on the pooled-only layer); GroupNorm statistics are accumulated per wave over the eight
 //    boxes of a sample and reduced once per sample (stats_tiles = 1).
-// Both kernels hand a whole sample over pre-split with the epilogue pieces of conv_split_common.h (triple: common.h:rf_gn_triple).
+// Both kernels hand a whole sample over pre-split with the epilogue pieces of conv_split_common.h (triple: common.h:rf_gn_triple) and stage through its
+// rf_norm_split8 / rf_store_hl; the launchers take the ConvArgs / SplitPreOut that conv_split_args.h builds and the calling entry point's name.
 #include "common.h"
-#include "conv_box.h"
-#include "conv_split_common.h"
+#include "conv_split_args.h"
 #include <type_traits>
 
 namespace {
@@ -88,10 +88,7 @@ __global__ __launch_bounds__(512, 4) void k_conv3_split_zc(ConvArgs a, SplitPreO
         const h8 zero = {0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
         for (int r = 0; r < 2; ++r)
-            if (r == 0 || tid < CS_VOX - 512) {
-                *reinterpret_cast<h8*>(img + vslot[r]) = st.in[r] ? st.ph[r] : zero;
-                *reinterpret_cast<h8*>(img + vslot[r] + CS_PLANE) = st.in[r] ? st.pl[r] : zero;
-            }
+            if (r == 0 || tid < CS_VOX - 512) rf_store_hl(img + vslot[r], CS_PLANE, st.in[r] ? st.ph[r] : zero, st.in[r] ? st.pl[r] : zero);
     };
 
     // ---- operand addressing.  wave = (zh, yq): planes z = 4 zh + mb, rows y = 2 yq + (ri >> 3), x = ri & 7; halo slot (z + 1, y + 1, x + 1)
@@ -409,15 +406,9 @@ __global__ __launch_bounds__(512, 4) void k_conv3_split_zcm(ConvArgs a, SplitPre
                 h = st.in[r] ? st.ph[r] : zero;
                 l = st.in[r] ? st.pl[r] : zero;
             } else {
-                float y[8];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) y[j] = st.in[r] ? fmaf(st.x[r][j] - af[j].x, af[j].y, af[j].z) : 0.f;
-                rf_split8(y, h, l);
+                rf_norm_split8(st.x[r], [&](int j) { return af[j]; }, h, l, st.in[r]);
             }
-            if (r == 0 || tid < CS_VOX - 512) {
-                *reinterpret_cast<h8*>(img + vslot[r]) = h;
-                *reinterpret_cast<h8*>(img + vslot[r] + CS_PLANE) = l;
-            }
+            if (r == 0 || tid < CS_VOX - 512) rf_store_hl(img + vslot[r], CS_PLANE, h, l);
         }
     };
 
@@ -655,16 +646,16 @@ bool rf_split_zc_takes(int cin, int n, int edge, int cout) {
     return cin == 8 && edge == 16 && cout > 0 && cout <= 16 && n >= 512;
 }
 
+// The calling entry point's name is NOT passed in here as it is to the other launchers: this symbol is exported and keeps its signature, and the name follows from the
+// form -- today the hand-over (po.out) is rf_conv3d_split_pre_k3_relu_pool_presplit's alone.  A third entry point that launches through here needs a `who` parameter
+// (and a changed symbol): with this guess its launch errors would carry one of these two names.
 int rf_split_zc_launch(const ConvArgs& a, const SplitPreOut& po, hipStream_t stream) {
-    const bool full = a.pool_mode != 2;
-    auto kern = full ? k_conv3_split_zc<true> : k_conv3_split_zc<false>;
-    static RfLdsOptIn opt[2];
-    if (int rc = opt[full].ensure(reinterpret_cast<const void*>(kern), ZC_LDS_BYTES, "rf_conv3d_split_pre_k3_relu")) return rc;
+    const char* who = po.out ? "rf_conv3d_split_pre_k3_relu_pool_presplit" : "rf_conv3d_split_pre_k3_relu";
     const int wgs = a.n < rf_persistent_wgs() ? a.n : rf_persistent_wgs();      // two workgroups per CU, whole samples each
     const int per = (a.n + wgs - 1) / wgs;
-    hipLaunchKernelGGL(kern, dim3((unsigned)((a.n + per - 1) / per)), dim3(512), ZC_LDS_BYTES, stream, a, po, per);
-    RF_CHECK_LAUNCH("rf_conv3d_split_pre_k3_relu");
-    return RF_OK;
+    const dim3 grid((unsigned)((a.n + per - 1) / per));
+    if (a.pool_mode != 2) return rf_launch<k_conv3_split_zc<true>>(who, grid, ZC_LDS_BYTES, ZC_LDS_BYTES, stream, a, po, per);
+    return rf_launch<k_conv3_split_zc<false>>(who, grid, ZC_LDS_BYTES, ZC_LDS_BYTES, stream, a, po, per);
 }
 
 // multi-chunk persistent form: up to 32 couts (16 per workgroup: the full-output form runs a 17..32-cout layer as two cout blocks on grid.y, each staging
@@ -677,17 +668,11 @@ bool rf_split_zcm_takes(int cin, int n, int edge, int cout) {
 
 template <bool PRE, int EPI, bool CH8 = false>
 static int zcm_launch(const ConvArgs& a, const SplitPreOut& po, hipStream_t stream, const char* who) {
-    auto kern = k_conv3_split_zcm<PRE, EPI, CH8>;
-    static RfLdsOptIn opt;
-    if (int rc = opt.ensure(reinterpret_cast<const void*>(kern), ZM_LDS_BYTES, who)) return rc;
     const long long boxes = (long long)a.n * (a.edge / 8) * (a.edge / 8) * (a.edge / 8);
     const int wgs = rf_persistent_wgs();                              // two workgroups per CU
     const unsigned cob_blocks = (unsigned)(a.cout16 / 16);
     const int per = (int)((boxes * cob_blocks + wgs - 1) / wgs);
-    hipLaunchKernelGGL(kern, dim3((unsigned)((boxes + per - 1) / per), cob_blocks), dim3(512), ZM_LDS_BYTES, stream, a, po, per, (int)boxes);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { rf_set_error("%s: launch failed: %s", who, hipGetErrorString(e)); return RF_E_LAUNCH; }
-    return RF_OK;
+    return rf_launch<k_conv3_split_zcm<PRE, EPI, CH8>>(who, dim3((unsigned)((boxes + per - 1) / per), cob_blocks), ZM_LDS_BYTES, ZM_LDS_BYTES, stream, a, po, per, (int)boxes);
 }
 
 // pre: the input is a pre-split tensor; po.pw_out set: the pointwise-head epilogue, else the full output (+ a.stats)

@@ -22,7 +22,8 @@
 // instantiated per pz for that.
 // Epilogue: accumulators -> ReLU -> LDS tile [cout][8^3] (rows of 517 floats: conflict-free scalar writes) -> 256-byte row stores; GroupNorm
 // statistics of the output (float64, fixed order) for the next layer -- or (rf_conv3d_up_split_presplit) the next layer's GroupNorm applied on
-// the spot and the output written pre-split (the hand-over epilogue of conv_split_common.h).
+// the spot and the output written pre-split (the hand-over epilogue of conv_split_common.h).  Every prologue stages through that header's staging step
+// (rf_stage8 / rf_norm_split8 / rf_store_hl); every launcher ends in common.h:rf_launch under the calling entry point's name.
 #include "conv_split_common.h"
 #include <type_traits>
 
@@ -169,18 +170,10 @@ __device__ __forceinline__ void us_stage_lowres(unsigned char* img, const float*
         const int hz = v / US_BZ, hy = (v / US_BY) % 6, hx = v % 6;
         const int z = (z0 >> 1) + hz - 1, y = (y0 >> 1) + hy - 1, x = (x0 >> 1) + hx - 1;
         const bool in = (unsigned)z < (unsigned)half && (unsigned)y < (unsigned)half && (unsigned)x < (unsigned)half;
-        float yv[8];
         const float* __restrict__ sp = src1 + ((size_t)n * c1 + cg * 8) * hvol + (in ? ((size_t)z * half + y) * half + x : 0);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const float4 af = aff[cg * 8 + j];
-            yv[j] = in ? fmaf(sp[(size_t)j * hvol] - af.x, af.y, af.z) : 0.f;
-        }
         h8 h, l;
-        rf_split8(yv, h, l);
-        unsigned char* p = img + cg * 2 * US_B_PLANE + v * 16;
-        *reinterpret_cast<h8*>(p) = h;
-        *reinterpret_cast<h8*>(p + US_B_PLANE) = l;
+        rf_norm_split8([&](int j) { return sp[(size_t)j * hvol]; }, [&](int j) { return aff[cg * 8 + j]; }, h, l, in);
+        rf_store_hl(img + cg * 2 * US_B_PLANE + v * 16, US_B_PLANE, h, l);
     }
 }
 
@@ -242,33 +235,17 @@ __global__ __launch_bounds__(512, 2) void k_conv3_up_split(UpSplitArgs a) {
 
     // ---- stage: all low-res channel groups (wave = group, lane = low-res voxel), the first skip chunk (thread = voxel)
     for (int cg = wave; cg < nB; cg += 8) {
-        float y[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const float4 af = aff[c0 + cg * 8 + j];
-            y[j] = fmaf((cg == wave ? xl[j] : a.src1[((size_t)n * c1 + cg * 8 + j) * 64 + lane]) - af.x, af.y, af.z);
-        }
         h8 h, l;
-        rf_split8(y, h, l);
+        rf_norm_split8([&](int j) { return cg == wave ? xl[j] : a.src1[((size_t)n * c1 + cg * 8 + j) * 64 + lane]; }, [&](int j) { return aff[c0 + cg * 8 + j]; }, h, l);
         const int slot = ((lane >> 4) + 1) * US_BZ + (((lane >> 2) & 3) + 1) * US_BY + (lane & 3) + 1;
-        unsigned char* p = lds + US_B_OFF + cg * 2 * US_B_PLANE + slot * 16;
-        *reinterpret_cast<h8*>(p) = h;
-        *reinterpret_cast<h8*>(p + US_B_PLANE) = l;
+        rf_store_hl(lds + US_B_OFF + cg * 2 * US_B_PLANE + slot * 16, US_B_PLANE, h, l);
     }
     const int vslot = ((tid >> 6) + 1) * US_SZ + (((tid >> 3) & 7) + 1) * US_SY + (tid & 7) + 1;     // this thread's voxel in the full-res halo box
     auto stage_store = [&](const float (&x)[8], int ca) {           // ca: chunk slot; past the last chunk: harmless re-staging of the last one
-        float y[8];
         const int cc = ca < nA ? ca : nA - 1;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const float4 af = aff[cc * 8 + j];
-            y[j] = fmaf(x[j] - af.x, af.y, af.z);
-        }
         h8 h, l;
-        rf_split8(y, h, l);
-        unsigned char* p = lds + (ca & 1) * US_A_BUF + vslot * 16;
-        *reinterpret_cast<h8*>(p) = h;
-        *reinterpret_cast<h8*>(p + US_A_PLANE) = l;
+        rf_norm_split8(x, [&](int j) { return aff[cc * 8 + j]; }, h, l);
+        rf_store_hl(lds + (ca & 1) * US_A_BUF + vslot * 16, US_A_PLANE, h, l);
     };
     if (nA > 0) stage_store(x0, 0);
 
@@ -367,17 +344,9 @@ __global__ __launch_bounds__(512, 2) void k_conv3_up_split(UpSplitArgs a) {
         auto convert_store = [&](int half) {
             if constexpr (PZ == 0) {
                 __builtin_amdgcn_sched_barrier(0);
-                float y[8];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const float4 af = aff[cx * 8 + j];
-                    y[j] = fmaf(x[j] - af.x, af.y, af.z);
-                }
                 h8 h, l;
-                rf_split8(y, h, l);
-                unsigned char* p = lds + ((ca + 1) & 1) * US_A_BUF + (vslot + half * 4 * US_SZ) * 16;
-                *reinterpret_cast<h8*>(p) = h;
-                *reinterpret_cast<h8*>(p + US_A_PLANE) = l;
+                rf_norm_split8(x, [&](int j) { return aff[cx * 8 + j]; }, h, l);
+                rf_store_hl(lds + ((ca + 1) & 1) * US_A_BUF + (vslot + half * 4 * US_SZ) * 16, US_A_PLANE, h, l);
                 __builtin_amdgcn_sched_barrier(0);
             }
         };
@@ -561,32 +530,16 @@ __global__ __launch_bounds__(512, 2) void k_conv3_up_split_pp(UpSplitArgs a) {
         }
         __syncthreads();
         if (wave < nB) {
-            float y[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float4 af = aff[c0 + cg * 8 + j];
-                y[j] = fmaf(xl[j] - af.x, af.y, af.z);
-            }
             h8 h, l;
-            rf_split8(y, h, l);
+            rf_norm_split8(xl, [&](int j) { return aff[c0 + cg * 8 + j]; }, h, l);
             const int slot = ((lane >> 4) + 1) * US_BZ + (((lane >> 2) & 3) + 1) * US_BY + (lane & 3) + 1;
-            unsigned char* p = lds + US_B_OFF + cg * 2 * US_B_PLANE + slot * 16;
-            *reinterpret_cast<h8*>(p) = h;
-            *reinterpret_cast<h8*>(p + US_B_PLANE) = l;
+            rf_store_hl(lds + US_B_OFF + cg * 2 * US_B_PLANE + slot * 16, US_B_PLANE, h, l);
         }
         {
-            float y[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float4 af = aff[j];
-                y[j] = fmaf(x0[j] - af.x, af.y, af.z);
-            }
             h8 h, l;
-            rf_split8(y, h, l);
+            rf_norm_split8(x0, [&](int j) { return aff[j]; }, h, l);
             const int vs = ((tid >> 6) + 1) * US_SZ + (((tid >> 3) & 7) + 1) * US_SY + (tid & 7) + 1;
-            unsigned char* p = lds + vs * 16;
-            *reinterpret_cast<h8*>(p) = h;
-            *reinterpret_cast<h8*>(p + US_A_PLANE) = l;
+            rf_store_hl(lds + vs * 16, US_A_PLANE, h, l);
         }
     }
 
@@ -788,9 +741,7 @@ __global__ __launch_bounds__(512, 2) void k_conv3_up_split_pp(UpSplitArgs a) {
                     asm volatile("" : "+v"(vs));
                     const int tix = vs;
                     vs = ((vs >> 6) + 1) * US_SZ + (((vs >> 3) & 7) + 1) * US_SY + (vs & 7) + 1;
-                    unsigned char* p = lds + ((ca + 1) & 1) * US_A_BUF + vs * 16;
-                    *reinterpret_cast<h8*>(p) = h;
-                    *reinterpret_cast<h8*>(p + US_A_PLANE) = l;
+                    rf_store_hl(lds + ((ca + 1) & 1) * US_A_BUF + vs * 16, US_A_PLANE, h, l);
                     if constexpr (BK == -2) {
                         float* tb = reinterpret_cast<float*>(lds + PP_AFF) + (sp ^ 1) * 384 + (tix < cin ? tix : cin - 1);
                         tb[0] = afn.x; tb[128] = afn.y; tb[256] = afn.z;
@@ -807,9 +758,7 @@ __global__ __launch_bounds__(512, 2) void k_conv3_up_split_pp(UpSplitArgs a) {
                     int ls = tid;
                     asm volatile("" : "+v"(ls));
                     ls = (((ls >> 4) & 3) + 1) * US_BZ + (((ls >> 2) & 3) + 1) * US_BY + (ls & 3) + 1;
-                    unsigned char* p = lds + US_B_OFF + cgb * 2 * US_B_PLANE + ls * 16;
-                    *reinterpret_cast<h8*>(p) = h;
-                    *reinterpret_cast<h8*>(p + US_B_PLANE) = l;
+                    rf_store_hl(lds + US_B_OFF + cgb * 2 * US_B_PLANE + ls * 16, US_B_PLANE, h, l);
                     __builtin_amdgcn_sched_barrier(0);
                 }
             };
@@ -1038,18 +987,7 @@ __global__ __launch_bounds__(512, NB >= 3 ? 2 : 4) void k_conv3_up_split_s4(UpSp
 #pragma unroll
             for (int j = 0; j < 8; ++j) x[j] = s0[(size_t)(ca * 8 + j) * 64];
         };
-        auto stage_store = [&](const float (&x)[8], int ca) {
-            float y[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float4 af = aff[ca * 8 + j];
-                y[j] = fmaf(x[j] - af.x, af.y, af.z);
-            }
-            h8 h, l;
-            rf_split8(y, h, l);
-            *reinterpret_cast<h8*>(myslot) = h;
-            *reinterpret_cast<h8*>(myslot + U4_A_PLANE) = l;
-        };
+        auto stage_store = [&](const float (&x)[8], int ca) { rf_stage8(myslot, U4_A_PLANE, x, [&](int j) { return aff[ca * 8 + j]; }); };
         // (z, y, x) = (2 qz + pz, 2 qy + py, 2 qx + px) in the sample's 6^3 halo cube (+1): the border plane is z = 3 pz, the interior plane z = 2 - pz
         const unsigned char* const abase = lds + ((ri >> 2) * 216 + (2 * ((ri >> 1) & 1) + py + 1) * 6 + 2 * (ri & 1) + px + 1) * 16;
         const int zplane[2] = {(3 * pz + 1) * 36 * 16, (3 - pz) * 36 * 16};
@@ -1108,16 +1046,7 @@ __global__ __launch_bounds__(512, NB >= 3 ? 2 : 4) void k_conv3_up_split_s4(UpSp
             const int ng = nB - cb0 < U4_BG ? nB - cb0 : U4_BG;
             if (cb0) __syncthreads();                               // everyone left the previous group
             if (scg < ng) {
-                float y[8];
-#pragma unroll
-                for (int jj = 0; jj < 8; ++jj) {
-                    const float4 af = aff[(cb0 + scg) * 8 + jj];
-                    y[jj] = fmaf(s1[(size_t)((cb0 + scg) * 8 + jj) * 8] - af.x, af.y, af.z);
-                }
-                h8 h, l;
-                rf_split8(y, h, l);
-                *reinterpret_cast<h8*>(myslot) = h;
-                *reinterpret_cast<h8*>(myslot + U4_B_PLANE) = l;
+                rf_stage8(myslot, U4_B_PLANE, [&](int j) { return s1[(size_t)((cb0 + scg) * 8 + j) * 8]; }, [&](int j) { return aff[(cb0 + scg) * 8 + j]; });
             }
             __syncthreads();
             for (int cg = 0; cg < ng; ++cg) {
@@ -1320,17 +1249,9 @@ __global__ __launch_bounds__(512, 4) void k_conv3_up_split_boxp(UpSplitArgs a, i
     };
     auto stage = [&](int buf) {                                     // registers -> normalised, split halo image
         if (!stager) return;
-        float yv[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const float4 af = *reinterpret_cast<const float4*>(lds + UP_AFF + (scg * 8 + j) * 16);
-            yv[j] = xin ? fmaf(xr[j] - af.x, af.y, af.z) : 0.f;                          // zero padding of the NORMALISED tensor
-        }
         h8 h, l;
-        rf_split8(yv, h, l);
-        unsigned char* p = lds + buf * UP_IMG + scg * 2 * US_B_PLANE + sv * 16;
-        *reinterpret_cast<h8*>(p) = h;
-        *reinterpret_cast<h8*>(p + US_B_PLANE) = l;
+        rf_norm_split8(xr, [&](int j) { return *reinterpret_cast<const float4*>(lds + UP_AFF + (scg * 8 + j) * 16); }, h, l, xin);
+        rf_store_hl(lds + buf * UP_IMG + scg * 2 * US_B_PLANE + sv * 16, US_B_PLANE, h, l);
     };
 
     // ---- this parity's weights: [group][tz][h | l], 16 VGPRs per group, resident for the whole run
@@ -1484,19 +1405,9 @@ __global__ __launch_bounds__(512, 2) void k_conv3_up_split_boxskip(UpSplitArgs a
         __syncthreads();                                           // the previous chunk's k-steps are done with the image
 #pragma unroll
         for (int r = 0; r < 2; ++r) {
-            float y[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float4 af = aff[ca * 8 + j];
-                y[j] = vin[r] ? fmaf(x[r][j] - af.x, af.y, af.z) : 0.f;
-            }
             h8 h, l;
-            rf_split8(y, h, l);
-            if (vsl[r] >= 0) {
-                unsigned char* p = lds + UK_A_OFF + vsl[r] * 16;
-                *reinterpret_cast<h8*>(p) = h;
-                *reinterpret_cast<h8*>(p + US_A_PLANE) = l;
-            }
+            rf_norm_split8(x[r], [&](int j) { return aff[ca * 8 + j]; }, h, l, vin[r]);
+            if (vsl[r] >= 0) rf_store_hl(lds + UK_A_OFF + vsl[r] * 16, US_A_PLANE, h, l);
         }
         __syncthreads();
         const unsigned char* buf = lds + UK_A_OFF + abase;
@@ -1597,39 +1508,24 @@ static UpSplitArgs up_split_pre_args(UpSplitArgs a, void* out_presplit, const fl
 }
 
 template <int NB>
-static int launch_up_split(const UpSplitArgs& a, hipStream_t stream) {
-    auto kern = k_conv3_up_split<NB>;
-    static RfLdsOptIn opt_in;
-    if (int rc = opt_in.ensure(reinterpret_cast<const void*>(kern), US_LDS_ALLOC, "rf_conv3d_up_split_k3_gn_relu")) return rc;
-    hipLaunchKernelGGL(kern, dim3((unsigned)a.n), dim3(512), US_LDS_ALLOC, stream, a);
-    RF_CHECK_LAUNCH("rf_conv3d_up_split_k3_gn_relu");
-    return RF_OK;
+static int launch_up_split(const UpSplitArgs& a, hipStream_t stream, const char* who) {
+    return rf_launch<k_conv3_up_split<NB>>(who, dim3((unsigned)a.n), US_LDS_ALLOC, US_LDS_ALLOC, stream, a);
 }
 
 // the persistent box form: two workgroups per CU (rf_persistent_wgs), each a run of boxes
 template <int NBG, int CGO>
-static int launch_up_split_boxp(const UpSplitArgs& a, int edge, int boxes, hipStream_t stream) {
-    auto kern = k_conv3_up_split_boxp<NBG, CGO>;
-    static RfLdsOptIn opt_in;
-    if (int rc = opt_in.ensure(reinterpret_cast<const void*>(kern), UP_LDS_BYTES, "rf_conv3d_up_split_k3_gn_relu_ch8")) return rc;
-    hipLaunchKernelGGL(kern, dim3((unsigned)rf_persistent_wgs()), dim3(512), UP_LDS_BYTES, stream, a, edge, boxes);
-    RF_CHECK_LAUNCH("rf_conv3d_up_split_k3_gn_relu");
-    return RF_OK;
+static int launch_up_split_boxp(const UpSplitArgs& a, int edge, int boxes, hipStream_t stream, const char* who) {
+    return rf_launch<k_conv3_up_split_boxp<NBG, CGO>>(who, dim3((unsigned)rf_persistent_wgs()), UP_LDS_BYTES, UP_LDS_BYTES, stream, a, edge, boxes);
 }
 
 // boxes with a skip source: NB of the weight image's nbt n-blocks per workgroup; LDS = the larger of the epilogue tile and the images (`img` bytes)
 template <int NB>
-static int launch_up_split_boxskip(const UpSplitArgs& a, int edge, unsigned boxes, int nbt, size_t img, hipStream_t stream) {
-    auto kern = k_conv3_up_split_boxskip<NB>;
-    static RfLdsOptIn opt_in;
+static int launch_up_split_boxskip(const UpSplitArgs& a, int edge, unsigned boxes, int nbt, size_t img, hipStream_t stream, const char* who) {
     const size_t tile = (size_t)(NB * 16) * UB_E_STRIDE * 4;
-    if (int rc = opt_in.ensure(reinterpret_cast<const void*>(kern), 160 * 1024, "rf_conv3d_up_split_k3_gn_relu")) return rc;
-    hipLaunchKernelGGL(kern, dim3(boxes, (unsigned)((nbt + NB - 1) / NB)), dim3(512), tile > img ? tile : img, stream, a, edge);
-    RF_CHECK_LAUNCH("rf_conv3d_up_split_k3_gn_relu");
-    return RF_OK;
+    return rf_launch<k_conv3_up_split_boxskip<NB>>(who, dim3(boxes, (unsigned)((nbt + NB - 1) / NB)), tile > img ? tile : img, 160 * 1024, stream, a, edge);
 }
 
-static int up_split_dispatch(UpSplitArgs& a, int c0, int c1, int n, int edge, int cout, void* stream);
+static int up_split_dispatch(UpSplitArgs& a, int c0, int c1, int n, int edge, int cout, hipStream_t stream, const char* who);
 
 // The persistent form (k_conv3_up_split_pp) takes the pre-split launches with four cout blocks, an even number (>= 4) of skip chunks and enough samples for
 // every CU to walk several: one workgroup per CU (134 KB of LDS, 256 VGPRs), RF_UP_PP_ROUNDS rounds of them (see rf_persistent_wgs on why more than one).
@@ -1640,13 +1536,9 @@ static bool up_split_pp_takes(int c0, int c1, int n, int cout) {
     return cout > 48 && cout <= 64 && cout % 8 == 0 && c0 >= 32 && c0 % 16 == 0 && c1 >= 8 && c1 % 8 == 0 && c1 <= 8 * US_MAX_CGB && n >= 1024;
 }
 
-static int launch_up_split_pp(const UpSplitArgs& a, hipStream_t stream) {
-    static RfLdsOptIn opt_in;
-    if (int rc = opt_in.ensure(reinterpret_cast<const void*>(k_conv3_up_split_pp), PP_LDS_ALLOC, "rf_conv3d_up_split_presplit")) return rc;
+static int launch_up_split_pp(const UpSplitArgs& a, hipStream_t stream, const char* who) {
     const int wgs = (rf_resident_wgs() / 2) * RF_UP_PP_ROUNDS;
-    hipLaunchKernelGGL(k_conv3_up_split_pp, dim3((unsigned)(a.n < wgs ? a.n : wgs)), dim3(512), PP_LDS_ALLOC, stream, a);
-    RF_CHECK_LAUNCH("rf_conv3d_up_split_presplit");
-    return RF_OK;
+    return rf_launch<k_conv3_up_split_pp>(who, dim3((unsigned)(a.n < wgs ? a.n : wgs)), PP_LDS_ALLOC, PP_LDS_ALLOC, stream, a);
 }
 
 extern "C" int rf_conv3d_up_split_k3_gn_relu(const float* src0, int c0, const float* src1, int c1, int n, int edge, const float* gn_affine,
@@ -1656,65 +1548,46 @@ extern "C" int rf_conv3d_up_split_k3_gn_relu(const float* src0, int c0, const fl
                c0, c1, n, edge, cout);
     RF_REQUIRE((c0 == 0 || src0) && src1 && gn_affine && w_packed && out, RF_E_INVALID, "rf_conv3d_up_split_k3_gn_relu: null pointer");
     UpSplitArgs a = up_split_args(src0, c0, src1, c1, n, gn_affine, w_packed, cout, out, stats);
-    return up_split_dispatch(a, c0, c1, n, edge, cout, stream);
+    return up_split_dispatch(a, c0, c1, n, edge, cout, (hipStream_t)stream, "rf_conv3d_up_split_k3_gn_relu");
 }
 
-static int up_split_dispatch(UpSplitArgs& a, int c0, int c1, int n, int edge, int cout, void* stream) {
+static int up_split_dispatch(UpSplitArgs& a, int c0, int c1, int n, int edge, int cout, hipStream_t stream, const char* who) {
     if (up_split_box_takes(c0, c1, n, edge, cout)) {
         const unsigned boxes = (unsigned)n * (edge / 8) * (edge / 8) * (edge / 8);
         const int nbq = rf_round_up(cout, 16) / 16;
         const size_t lds_bytes = (size_t)(nbq * 16) * UB_E_STRIDE * 4 > (size_t)(c1 / 8) * 2 * US_B_PLANE ? (size_t)(nbq * 16) * UB_E_STRIDE * 4 : (size_t)(c1 / 8) * 2 * US_B_PLANE;
         if (a.out_ch8 && (c1 == 8 || c1 == 16) && (cout == 8 || cout == 16) && boxes >= 2048 && (long long)cout * edge * edge * edge < (1ll << 28)) {
             // persistent form (channel-interleaved output only)
-            if (c1 == 16 && cout == 16) return launch_up_split_boxp<2, 2>(a, edge, (int)boxes, (hipStream_t)stream);
-            if (c1 == 16) return launch_up_split_boxp<2, 1>(a, edge, (int)boxes, (hipStream_t)stream);
-            if (cout == 16) return launch_up_split_boxp<1, 2>(a, edge, (int)boxes, (hipStream_t)stream);
-            return launch_up_split_boxp<1, 1>(a, edge, (int)boxes, (hipStream_t)stream);
-        } else if (nbq == 1) {
-            hipLaunchKernelGGL(k_conv3_up_split_box<1>, dim3(boxes), dim3(512), lds_bytes, (hipStream_t)stream, a, edge);
-        } else {
-            static RfLdsOptIn opt_in;
-            if (int rc = opt_in.ensure(reinterpret_cast<const void*>(k_conv3_up_split_box<2>), (int)lds_bytes, "rf_conv3d_up_split_k3_gn_relu")) return rc;
-            hipLaunchKernelGGL(k_conv3_up_split_box<2>, dim3(boxes), dim3(512), lds_bytes, (hipStream_t)stream, a, edge);
+            if (c1 == 16 && cout == 16) return launch_up_split_boxp<2, 2>(a, edge, (int)boxes, stream, who);
+            if (c1 == 16) return launch_up_split_boxp<2, 1>(a, edge, (int)boxes, stream, who);
+            if (cout == 16) return launch_up_split_boxp<1, 2>(a, edge, (int)boxes, stream, who);
+            return launch_up_split_boxp<1, 1>(a, edge, (int)boxes, stream, who);
         }
-        RF_CHECK_LAUNCH("rf_conv3d_up_split_k3_gn_relu");
-        return RF_OK;
+        // one n-block: the tile (16 couts) and the images (c1 <= 8 US_MAX_CGB) both stay below what a kernel gets without asking
+        static_assert(16 * UB_E_STRIDE * 4 <= 64 * 1024 && US_MAX_CGB * 2 * US_B_PLANE <= 64 * 1024, "k_conv3_up_split_box<1> is launched without an LDS opt-in");
+        if (nbq == 1) return rf_launch<k_conv3_up_split_box<1>>(who, dim3(boxes), lds_bytes, 0, stream, a, edge);
+        return rf_launch<k_conv3_up_split_box<2>>(who, dim3(boxes), lds_bytes, 32 * UB_E_STRIDE * 4, stream, a, edge);
     }
     if (up_split_boxskip_takes(c0, c1, n, edge, cout)) {
         const unsigned boxes = (unsigned)n * (edge / 8) * (edge / 8) * (edge / 8);
         const int nbt = rf_round_up(cout, 16) / 16;
         const size_t img = (size_t)US_A_BUF + (size_t)(c1 / 8) * 2 * US_B_PLANE;
-        if (nbt == 1) return launch_up_split_boxskip<1>(a, edge, boxes, nbt, img, (hipStream_t)stream);
-        if (nbt == 2 || nbt == 4) return launch_up_split_boxskip<2>(a, edge, boxes, nbt, img, (hipStream_t)stream);
-        return launch_up_split_boxskip<3>(a, edge, boxes, nbt, img, (hipStream_t)stream);
+        if (nbt == 1) return launch_up_split_boxskip<1>(a, edge, boxes, nbt, img, stream, who);
+        if (nbt == 2 || nbt == 4) return launch_up_split_boxskip<2>(a, edge, boxes, nbt, img, stream, who);
+        return launch_up_split_boxskip<3>(a, edge, boxes, nbt, img, stream, who);
     }
     if (edge == 4) {
         const int nbt = rf_round_up(cout, 16) / 16;
-        if (nbt == 4 || nbt == 3) {
-            // all 64 (48: nf = 12) couts in one workgroup (256 VGPRs, 132 KB LDS, one workgroup per CU -- the shape of the 8^3 kernel): the samples are
-            // staged and converted ONCE instead of once per 16-cout block
-            static RfLdsOptIn opt_wide4, opt_wide3;
-            const int lds_wide = nbt * 16 * U4_E_STRIDE * 4;
-            if (nbt == 4) {
-                if (int rc = opt_wide4.ensure(reinterpret_cast<const void*>(k_conv3_up_split_s4<4, true>), lds_wide, "rf_conv3d_up_split_k3_gn_relu")) return rc;
-                hipLaunchKernelGGL((k_conv3_up_split_s4<4, true>), dim3((unsigned)((n + 7) / 8), 1u), dim3(512), lds_wide, (hipStream_t)stream, a);
-            } else {
-                if (int rc = opt_wide3.ensure(reinterpret_cast<const void*>(k_conv3_up_split_s4<3, true>), lds_wide, "rf_conv3d_up_split_k3_gn_relu")) return rc;
-                hipLaunchKernelGGL((k_conv3_up_split_s4<3, true>), dim3((unsigned)((n + 7) / 8), 1u), dim3(512), lds_wide, (hipStream_t)stream, a);
-            }
-            RF_CHECK_LAUNCH("rf_conv3d_up_split_k3_gn_relu");
-            return RF_OK;
-        }
-        static RfLdsOptIn opt_in;
+        const dim3 wide((unsigned)((n + 7) / 8), 1u);
+        // all 64 (48: nf = 12) couts in one workgroup (256 VGPRs, 132 KB LDS, one workgroup per CU -- the shape of the 8^3 kernel): the samples are
+        // staged and converted ONCE instead of once per 16-cout block
+        if (nbt == 4) return rf_launch<k_conv3_up_split_s4<4, true>>(who, wide, 4 * 16 * U4_E_STRIDE * 4, 4 * 16 * U4_E_STRIDE * 4, stream, a);
+        if (nbt == 3) return rf_launch<k_conv3_up_split_s4<3, true>>(who, wide, 3 * 16 * U4_E_STRIDE * 4, 3 * 16 * U4_E_STRIDE * 4, stream, a);
         // 16 couts per workgroup: the 32-cout instance needs more than the 128 VGPRs that four waves per SIMD allow (35-45 spills) and was
         // no faster (629-641 us against 610 on dec0)
-        if (int rc = opt_in.ensure(reinterpret_cast<const void*>(k_conv3_up_split_s4<1, true>), U4_LDS_BYTES, "rf_conv3d_up_split_k3_gn_relu")) return rc;
-        hipLaunchKernelGGL((k_conv3_up_split_s4<1, true>), dim3((unsigned)((n + 7) / 8), (unsigned)nbt), dim3(512), U4_LDS_BYTES,
-                           (hipStream_t)stream, a);
-        RF_CHECK_LAUNCH("rf_conv3d_up_split_k3_gn_relu");
-        return RF_OK;
+        return rf_launch<k_conv3_up_split_s4<1, true>>(who, dim3((unsigned)((n + 7) / 8), (unsigned)nbt), U4_LDS_BYTES, U4_LDS_BYTES, stream, a);
     }
-    return rf_round_up(cout, 16) == 48 ? launch_up_split<3>(a, (hipStream_t)stream) : launch_up_split<4>(a, (hipStream_t)stream);
+    return rf_round_up(cout, 16) == 48 ? launch_up_split<3>(a, stream, who) : launch_up_split<4>(a, stream, who);
 }
 
 // The whole-sample decoder form with its output handed to the NEXT SingleConv pre-split: relu(conv(GN(x))) of 8^3 samples, then the
@@ -1734,8 +1607,8 @@ extern "C" int rf_conv3d_up_split_presplit(const float* src0, int c0, const floa
     RF_REQUIRE((c0 == 0 || src0) && src1 && gn_affine && w_packed && out_presplit && next_gamma && next_beta, RF_E_INVALID, "rf_conv3d_up_split_presplit: null pointer");
     const UpSplitArgs a = up_split_pre_args(up_split_args(src0, c0, src1, c1, n, gn_affine, w_packed, cout, nullptr, stats), out_presplit, next_gamma, next_beta,
                                             next_groups, eps, 0);
-    if (up_split_pp_takes(c0, c1, n, cout)) return launch_up_split_pp(a, (hipStream_t)stream);
-    return rf_round_up(cout, 16) == 48 ? launch_up_split<3>(a, (hipStream_t)stream) : launch_up_split<4>(a, (hipStream_t)stream);
+    if (up_split_pp_takes(c0, c1, n, cout)) return launch_up_split_pp(a, (hipStream_t)stream, "rf_conv3d_up_split_presplit");
+    return rf_round_up(cout, 16) == 48 ? launch_up_split<3>(a, (hipStream_t)stream, "rf_conv3d_up_split_presplit") : launch_up_split<4>(a, (hipStream_t)stream, "rf_conv3d_up_split_presplit");
 }
 
 // The same with the voxel slots of the output in PARITY-MAJOR order (UpSplitArgs::pre_pm; consumer: rf_conv3d_split_pre_pm_k3_relu): the persistent kernel
@@ -1754,7 +1627,7 @@ extern "C" int rf_conv3d_up_split_presplit_pm(const float* src0, int c0, const f
     RF_REQUIRE(src0 && src1 && gn_affine && w_packed && out_presplit_pm && next_gamma && next_beta, RF_E_INVALID, "rf_conv3d_up_split_presplit_pm: null pointer");
     const UpSplitArgs a = up_split_pre_args(up_split_args(src0, c0, src1, c1, n, gn_affine, w_packed, cout, nullptr, stats), out_presplit_pm, next_gamma, next_beta,
                                             next_groups, eps, 1);
-    return launch_up_split_pp(a, (hipStream_t)stream);
+    return launch_up_split_pp(a, (hipStream_t)stream, "rf_conv3d_up_split_presplit_pm");
 }
 
 // rf_conv3d_up_split_k3_gn_relu with the output CHANNEL-INTERLEAVED, [n][cout / 8][edge^3][8 channels] fp32 ("ch8"), for a consumer that stages the 8 channels
@@ -1774,5 +1647,5 @@ extern "C" int rf_conv3d_up_split_k3_gn_relu_ch8(const float* src0, int c0, cons
     RF_REQUIRE(src1 && gn_affine && w_packed && out_ch8, RF_E_INVALID, "rf_conv3d_up_split_k3_gn_relu_ch8: null pointer");
     UpSplitArgs a = up_split_args(src0, c0, src1, c1, n, gn_affine, w_packed, cout, out_ch8, stats);
     a.out_ch8 = 1;
-    return up_split_dispatch(a, c0, c1, n, edge, cout, stream);
+    return up_split_dispatch(a, c0, c1, n, edge, cout, (hipStream_t)stream, "rf_conv3d_up_split_k3_gn_relu_ch8");
 }

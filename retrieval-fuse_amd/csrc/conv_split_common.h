@@ -1,5 +1,7 @@
-// Shared by the split-operand kernels (conv3d_split.hip, conv3d_split_zc.hip, conv3d_up_split.hip): the halo-box image in LDS, the pre-split output and
-// the HAND-OVER EPILOGUE that writes it.  The operand format itself is split_operand.h; the triple from (sum, sum of squares) is rf_gn_triple (common.h).
+// Shared by the split-operand kernels (conv3d_split.hip, conv3d_split_zc.hip, conv3d_up_split.hip): the halo-box image in LDS, the STAGING STEP of the
+// prologue that fills it (rf_stage8 = rf_norm_split8 + rf_store_hl), the pre-split output (SplitPreOut and its makers) and the HAND-OVER EPILOGUE that
+// writes it.  The operand format itself is split_operand.h; the triple from (sum, sum of squares) is rf_gn_triple (common.h); the host side of the
+// conv3d_split entry points (ConvArgs builders, pointer refusals) is conv_split_args.h and the launch tail is rf_launch (common.h).
 #pragma once
 #include "common.h"
 #include "split_operand.h"
@@ -20,18 +22,63 @@ constexpr int CS_LDS_BYTES = 2 * CS_BUF;                         // 66,560
 // pre-split OUTPUT (whole 8^3 samples, 16 couts in one workgroup): the NEXT layer's GroupNorm -- its gamma / beta / groups / eps over this layer's couts --
 // is applied in the epilogue from the sample's own statistics and the result written as that layer's pre-split input; null: off
 struct SplitPreOut {
-    h8* out;
-    const float* gamma;
-    const float* beta;
-    int groups;
-    float eps;
+    h8* out = nullptr;
+    const float* gamma = nullptr;
+    const float* beta = nullptr;
+    int groups = 0;
+    float eps = 0.f;
     // ... or the final decoder's pointwise head (reference model/refinement.py:48-61: Conv3d(nf, 1, 1) + bias -> tanh -> network_pred_to_df) applied to the
     // ReLU'd output in the epilogue: pw_out [n][1][edge^3] = (tanh(sum_c w[c] y[c] + b) + post_add) * post_mul, the nf-channel tensor is never written
-    float* pw_out;
-    const float* pw_w;
-    const float* pw_b;
-    float post_add, post_mul;
+    float* pw_out = nullptr;
+    const float* pw_w = nullptr;
+    const float* pw_b = nullptr;
+    float post_add = 0.f, post_mul = 0.f;
+
+    static SplitPreOut presplit(void* out_presplit, const float* next_gamma, const float* next_beta, int next_groups, float eps) {
+        SplitPreOut po;
+        po.out = reinterpret_cast<h8*>(out_presplit); po.gamma = next_gamma; po.beta = next_beta; po.groups = next_groups; po.eps = eps;
+        return po;
+    }
+    static SplitPreOut pointwise(float* out1, const float* pw_w, const float* pw_b, float post_add, float post_mul) {
+        SplitPreOut po;
+        po.pw_out = out1; po.pw_w = pw_w; po.pw_b = pw_b; po.post_add = post_add; po.post_mul = post_mul;
+        return po;
+    }
 };
+
+// ------------------------------------------------------------------------------------------------------- the staging step of the prologue
+// Every kernel of the family stages its input the same way: 8 channels of one voxel, y = (x - center) * scale + shift by the channels' GroupNorm triples, zeros
+// where the voxel is padding of the NORMALISED tensor, split, h into the voxel's 16-byte slot and l one plane further on.  What is scheduling stays with the
+// kernel: sched_barriers, opaque copies of the thread index, the slot arithmetic, which waves stage, guards on the stores.
+
+// the two stores alone (also: pre-split copies, which stage h / l they did not compute); `plane`: bytes from the h plane to the l plane
+__device__ __forceinline__ void rf_store_hl(unsigned char* slot, int plane, const h8& h, const h8& l) {
+    *reinterpret_cast<h8*>(slot) = h;
+    *reinterpret_cast<h8*>(slot + plane) = l;
+}
+// channel j of the staged voxel: x is the 8 register-staged values, or a callable for a site that loads the value where it is used
+__device__ __forceinline__ float rf_chan(const float (&x)[8], int j) { return x[j]; }
+template <class X>
+__device__ __forceinline__ auto rf_chan(X&& x, int j) -> decltype(x(j)) { return x(j); }
+// normalise (triple(j) -> float4 of channel j; !live: the zero padding of the NORMALISED tensor) and split, for a kernel that guards its stores or forms the
+// slot address after the conversion (the order of the source is the order hipcc schedules from)
+template <class X, class Triple>
+__device__ __forceinline__ void rf_norm_split8(X&& x, Triple&& triple, h8& h, h8& l, bool live = true) {
+    float y[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const float4 af = triple(j);
+        y[j] = live ? fmaf(rf_chan(x, j) - af.x, af.y, af.z) : 0.f;
+    }
+    rf_split8(y, h, l);
+}
+// the whole step
+template <class X, class Triple>
+__device__ __forceinline__ void rf_stage8(unsigned char* slot, int plane, X&& x, Triple&& triple, bool live = true) {
+    h8 h, l;
+    rf_norm_split8(x, triple, h, l, live);
+    rf_store_hl(slot, plane, h, l);
+}
 
 // ------------------------------------------------------------------------------------------------------- the hand-over epilogue
 // ReLU'd tile [cout][8^3] in LDS -> per-channel float64 sums -> the next layer's GroupNorm triples -> normalise, split, [h | l] slots.  Three pieces that a
@@ -68,6 +115,7 @@ __device__ __forceinline__ float4 rf_group_triple(const double2* chst, int c, in
 template <int VOX, class Value>
 __device__ __forceinline__ void rf_presplit_store(h8* __restrict__ o, int cgroups, const float4* trip, Value&& value) {
     for (int sg = 0; sg < cgroups; ++sg) {
+        // rf_norm_split8 written out: through it k_conv3_split_zc<true> spills one more VGPR (12 against 11); keep the two in step
         float y[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
@@ -76,7 +124,6 @@ __device__ __forceinline__ void rf_presplit_store(h8* __restrict__ o, int cgroup
         }
         h8 h, l;
         rf_split8(y, h, l);
-        o[(size_t)sg * 2 * VOX] = h;
-        o[(size_t)sg * 2 * VOX + VOX] = l;
+        rf_store_hl(reinterpret_cast<unsigned char*>(o + (size_t)sg * 2 * VOX), VOX * 16, h, l);
     }
 }

@@ -10,28 +10,25 @@ OUT = REPO / 'tools' / '_haz'
 ENTRY = '''
 extern "C" int zcm_run(const void* src, int pre, const float* aff, const void* wp, float* out, float* pw_out, const float* pw_w, const float* pw_b, int cin, int n, int edge, void* stream,
                        int cout, float* pool_out, double* stats, double* pool_stats) {
-    ConvArgs a;
-    a.src0 = reinterpret_cast<const float*>(src); a.src1 = nullptr; a.affine = reinterpret_cast<const float4*>(aff); a.wp = reinterpret_cast<const float*>(wp); a.out = out;
-    a.c0 = cin; a.c1 = 0; a.n = n; a.edge = edge; a.cout = cout; a.cin4 = cin; a.cout16 = (cout + 15) / 16 * 16; a.stats = reinterpret_cast<double2*>(stats); a.stats_tiles = 1;
-    a.pool_out = pool_out; a.pool_stats = reinterpret_cast<double2*>(pool_stats); a.pool_mode = pool_out ? 1 : 0; a.floor = 0.f;
-    const SplitPreOut po{nullptr, nullptr, nullptr, 0, 0.f, pw_out, pw_w, pw_b, 1.0f, 0.5f};
-    return rf_split_zcm_launch(a, po, pre != 0, (hipStream_t)stream, "zcm_run");
+    ConvArgs a = split_with_outputs(split_conv_args(src, cin, n, edge, aff, wp, cout), out, stats, pool_out, pool_stats, 1);
+    a.src1 = g_dbg;
+    return rf_split_zcm_launch(a, SplitPreOut::pointwise(pw_out, pw_w, pw_b, 1.0f, 0.5f), pre != 0, (hipStream_t)stream, "zcm_run");
 }
 '''
 MF = "auto mf = [](const h8& x, const h8& y, const f32x4& c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(x, y, c, 0, 0, 0); };"
 NO_MF = "auto mf = [](const h8& x, const h8& y, const f32x4& c) { f32x4 r = c; r[0] += (float)x[0] * (float)y[0]; return r; };"
 MID = "            lds_barrier();                                            // MID: R1 in place, R0 free"
-LOADS_PRE = """                st.ph[r] = *reinterpret_cast<const h8*>(p + (size_t)off * 16);
-                st.pl[r] = *reinterpret_cast<const h8*>(p + (vol + off) * 16);"""
+LOADS_PRE = """                st.ph[r] = *reinterpret_cast<const h8*>(p + off * 16u);
+                st.pl[r] = *reinterpret_cast<const h8*>(p + ((unsigned)vol + off) * 16u);"""
 NO_LOADS_PRE = """                st.ph[r] = h8{(_Float16)(float)off, 0, 0, 0, 0, 0, 0, 0};
                 st.pl[r] = h8{(_Float16)(float)r, 0, 0, 0, 0, 0, 0, 0};"""
-LOADS_F32 = "                for (int j = 0; j < 8; ++j) st.x[r][j] = p[(size_t)j * vol];"
+LOADS_F32 = "                for (int j = 0; j < 8; ++j) st.x[r][j] = p[(unsigned)j * (unsigned)vol + off];"
 NO_LOADS_F32 = "                for (int j = 0; j < 8; ++j) st.x[r][j] = (float)(off + j);"
-CONV = "                for (int j = 0; j < 8; ++j) y[j] = st.in[r] ? fmaf(st.x[r][j] - af[j].x, af[j].y, af[j].z) : 0.f;\n                cs_split8(y, h, l);"
+CONV = "                rf_norm_split8(st.x[r], [&](int j) { return af[j]; }, h, l, st.in[r]);"
 NO_CONV = "                for (int j = 0; j < 8; ++j) { h[j] = (_Float16)st.x[r][j]; l[j] = (_Float16)af[j].y; }"
-W1 = "            const h8 w1 = wsrc[(size_t)ca * wstride + wsrc1];        // R1 of this chunk: lands under pass 0"
+W1 = "            const h8 w1 = (wsrc + (size_t)ca * wstride)[(unsigned)wsrc1];     // R1 of this chunk: lands under pass 0"
 NO_W1 = "            const h8 w1 = h8{(_Float16)(float)ca, 0, 0, 0, 0, 0, 0, 0};"
-W0 = "            const h8 w0 = wsrc[(size_t)nca * wstride + wsrc0];       // R0 of the next chunk: lands under pass 1"
+W0 = "            const h8 w0 = (wsrc + (size_t)nca * wstride)[(unsigned)wsrc0];    // R0 of the next chunk: lands under pass 1"
 NO_W0 = "            const h8 w0 = h8{(_Float16)(float)nca, 0, 0, 0, 0, 0, 0, 0};"
 SST = "            stage_store(st, nbox, nca, other);\n            if (tid < 384)"
 NO_SST = "            if (box < 0) stage_store(st, nbox, nca, other);\n            if (tid < 384)"
@@ -65,7 +62,7 @@ def build(names=None):
             src = src.replace(old, new)
         src = head + src
         p = OUT / ('zcm_%s.hip' % name)
-        p.write_text(src + ENTRY.replace('a.src1 = nullptr;', 'a.src1 = pw_b ? nullptr : nullptr; a.src1 = g_dbg;').replace('extern "C" int zcm_run', 'static float* g_dbg = nullptr;\nextern "C" void zcm_dbg(float* p) { g_dbg = p; }\nextern "C" int zcm_run'))
+        p.write_text(src + ENTRY.replace('extern "C" int zcm_run', 'static float* g_dbg = nullptr;\nextern "C" void zcm_dbg(float* p) { g_dbg = p; }\nextern "C" int zcm_run'))
         obj = OUT / ('zcm_%s.o' % name)
         subprocess.run(['/opt/rocm/bin/hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-I', str(CSRC), '-c', str(p), '-o', str(obj)], check=True)
         subprocess.run(['/opt/rocm/bin/hipcc', '--offload-arch=gfx950', '-shared', '-fPIC', '-o', str(OUT / ('libzcm_%s.so' % name)), str(obj), str(CSRC / 'build' / 'capi.o')], check=True)
