@@ -54,17 +54,13 @@ static int fold_check(const char* who, const void* a, const void* b2, int b, int
 extern "C" int rf_unfold3d(const float* x, int b, int c, int s, int e, float* rows, void* stream) {
     int rc = fold_check("rf_unfold3d", x, rows, b, c, s, e);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_unfold3d, dim3(grid_for((size_t)b * c * s * s * s)), dim3(256), 0, (hipStream_t)stream, x, b, c, s, e, rows);
-    RF_CHECK_LAUNCH("rf_unfold3d");
-    return RF_OK;
+    return rf_launch<k_unfold3d>("rf_unfold3d", dim3(grid_for((size_t)b * c * s * s * s)), dim3(256), (hipStream_t)stream, x, b, c, s, e, rows);
 }
 
 extern "C" int rf_fold3d(const float* rows, int b, int c, int s, int e, float* x, void* stream) {
     int rc = fold_check("rf_fold3d", rows, x, b, c, s, e);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_fold3d, dim3(grid_for((size_t)b * c * s * s * s)), dim3(256), 0, (hipStream_t)stream, rows, b, c, s, e, x);
-    RF_CHECK_LAUNCH("rf_fold3d");
-    return RF_OK;
+    return rf_launch<k_fold3d>("rf_fold3d", dim3(grid_for((size_t)b * c * s * s * s)), dim3(256), (hipStream_t)stream, rows, b, c, s, e, x);
 }
 
 // p_rows[(bb*r^3 + prow)][k][c][e^3]  <-  retrieved features of (bb, k) at the attention patch prow
@@ -99,10 +95,8 @@ extern "C" int rf_attn_gather_retrieved(const float* src, int src_layout, int b,
     RF_REQUIRE(src_layout == 0 || (src_layout == 1 && t > 0 && s % t == 0 && t % e == 0), RF_E_INVALID,
                "rf_attn_gather_retrieved: bad layout %d / patch edge %d", src_layout, t);
     if (src_layout == 0) t = s;
-    hipLaunchKernelGGL(k_attn_gather, dim3(grid_for((size_t)b * k * c * s * s * s)), dim3(256), 0, (hipStream_t)stream, src, src_layout, b, k, c,
-                       s, e, t, p_rows);
-    RF_CHECK_LAUNCH("rf_attn_gather_retrieved");
-    return RF_OK;
+    return rf_launch<k_attn_gather>("rf_attn_gather_retrieved", dim3(grid_for((size_t)b * k * c * s * s * s)), dim3(256), (hipStream_t)stream, src, src_layout, b, k,
+                                    c, s, e, t, p_rows);
 }
 
 // ------------------------------------------------------------------------------------------------- fused attention
@@ -147,9 +141,6 @@ extern "C" int rf_attn_fuse(const float* x, const float* p, const float* xf, con
     RF_REQUIRE(f >= 1 && f <= 128, RF_E_UNSUPPORTED, "rf_attn_fuse: feature width %d outside 1..128", f);
     RF_REQUIRE(mode == RF_ATTN_SOFTMAX || (mode == RF_ATTN_GUMBEL_HARD && noise), RF_E_INVALID,
                "rf_attn_fuse: Gumbel-hard mode needs the noise tensor");
-    const int want = (b + 3) / 4;
-    hipLaunchKernelGGL(k_attn_fuse, dim3(want < 4096 ? want : 4096), dim3(256), 0, (hipStream_t)stream, x, p, xf, pf, noise, b, k, d, f, mode,
-                       sharpness, out, scores_out, weights_out);
-    RF_CHECK_LAUNCH("rf_attn_fuse");
-    return RF_OK;
+    return rf_launch<k_attn_fuse>("rf_attn_fuse", dim3(rf_blocks(b, 4, 4096)), dim3(256), (hipStream_t)stream, x, p, xf, pf, noise, b, k, d, f, mode, sharpness, out,
+                                  scores_out, weights_out);
 }

@@ -83,9 +83,7 @@ extern "C" int rf_attn_mlp_pack(const float* w1, const float* b1, const float* w
     a.w[0] = w1; a.w[1] = w2; a.w[2] = w3; a.w[3] = w4;
     a.b[0] = b1; a.b[1] = b2; a.b[2] = b3; a.b[3] = b4;
     a.img = packed; a.n_in = n_in;
-    hipLaunchKernelGGL(k_attn_mlp_pack, dim3(256), dim3(256), 0, (hipStream_t)stream, a);
-    RF_CHECK_LAUNCH("rf_attn_mlp_pack");
-    return RF_OK;
+    return rf_launch<k_attn_mlp_pack>("rf_attn_mlp_pack", dim3(256), dim3(256), (hipStream_t)stream, a);
 }
 
 // ------------------------------------------------------------------------------------------------ fused MLP
@@ -279,9 +277,7 @@ extern "C" int rf_attn_mlp_split_pack(const float* w1, const float* w2, const fl
     RF_REQUIRE(n_in >= 16 && n_in <= AM_HID && n_in % 16 == 0, RF_E_UNSUPPORTED, "rf_attn_mlp_split_pack: n_in %d must be a multiple of 16 in 16..128", n_in);
     AmsPackArgs a;
     a.w[0] = w1; a.w[1] = w2; a.w[2] = w3; a.w[3] = w4; a.img = packed; a.n_in = n_in;
-    hipLaunchKernelGGL(k_attn_mlp_split_pack, dim3(256), dim3(256), 0, (hipStream_t)stream, a);
-    RF_CHECK_LAUNCH("rf_attn_mlp_split_pack");
-    return RF_OK;
+    return rf_launch<k_attn_mlp_split_pack>("rf_attn_mlp_split_pack", dim3(256), dim3(256), (hipStream_t)stream, a);
 }
 
 // 4 activation values (one D register quartet) -> 4 halves of the h and of the l piece, at positions o..o+3.  On register PAIRS (v_pk_mul_f32 for the two
@@ -424,20 +420,9 @@ __global__ __launch_bounds__(AMS_WAVES * 64) void k_attn_mlp_split(AmArgs a) {
 }
 
 static int am_launch(const AmArgs& a, hipStream_t st) {
-    const int lds = 2 * AM_BUF_FLOATS * (int)sizeof(float);
-    static RfLdsOptIn opt_in;
-    if (int rc = opt_in.ensure(reinterpret_cast<const void*>(k_attn_mlp), lds, "rf_attn_mlp")) return rc;
-    const int nwt = (a.ntiles + AM_WAVES - 1) / AM_WAVES;
-    if (a.img2) {
-        static RfLdsOptIn opt_in2;
-        if (int rc = opt_in2.ensure(reinterpret_cast<const void*>(k_attn_mlp_split), lds, "rf_attn_mlp")) return rc;
-        const int nwt2 = (a.ntiles + AMS_WAVES - 1) / AMS_WAVES;
-        hipLaunchKernelGGL(k_attn_mlp_split, dim3(nwt2 < 256 ? nwt2 : 256), dim3(AMS_WAVES * 64), lds, st, a);
-    } else {
-        hipLaunchKernelGGL(k_attn_mlp, dim3(nwt < 256 ? nwt : 256), dim3(AM_WAVES * 64), lds, st, a);
-    }
-    RF_CHECK_LAUNCH("rf_attn_mlp");
-    return RF_OK;
+    constexpr size_t lds = 2 * AM_BUF_FLOATS * sizeof(float);
+    if (a.img2) return rf_launch<k_attn_mlp_split>("rf_attn_mlp", dim3(rf_blocks(a.ntiles, AMS_WAVES, 256)), dim3(AMS_WAVES * 64), lds, lds, st, a);
+    return rf_launch<k_attn_mlp>("rf_attn_mlp", dim3(rf_blocks(a.ntiles, AM_WAVES, 256)), dim3(AM_WAVES * 64), lds, lds, st, a);
 }
 
 static int am_rows(const float* x, int rows, int n_in, const float* packed, const float* packed_split, float* out, void* stream);
@@ -537,11 +522,8 @@ static int attn_weights_launch(const float* xf, const float* pf, const float* no
     RF_REQUIRE(xf && pf && weights && switches && rows > 0, RF_E_INVALID, "%s: bad arguments", who);
     RF_REQUIRE(k >= 1 && k <= RF_MAX_K, RF_E_UNSUPPORTED, "%s: K=%d outside 1..%d", who, k, RF_MAX_K);
     RF_REQUIRE(f >= 1 && f <= 128, RF_E_UNSUPPORTED, "%s: feature width %d outside 1..128", who, f);
-    const int want = (rows + 255) / 256;
-    hipLaunchKernelGGL(k_attn_weights, dim3(want < 8192 ? want : 8192), dim3(256), 0, (hipStream_t)stream, xf, pf, noise, rng, rows, k, f, mode, sharpness,
-                       weights, switches, scores_out, noise_out);
-    RF_CHECK_LAUNCH(who);
-    return RF_OK;
+    return rf_launch<k_attn_weights>(who, dim3(rf_blocks(rows, 256, 8192)), dim3(256), (hipStream_t)stream, xf, pf, noise, rng, rows, k, f, mode, sharpness, weights,
+                                     switches, scores_out, noise_out);
 }
 
 extern "C" int rf_attn_weights(const float* xf, const float* pf, const float* noise, int rows, int k, int f, int mode, float sharpness,
@@ -594,9 +576,6 @@ extern "C" int rf_attn_blend(const float* x, const float* retrieved, int b, int 
     RF_REQUIRE(x && retrieved && weights && switches && out && b > 0 && k > 0 && c > 0, RF_E_INVALID, "rf_attn_blend: bad arguments");
     RF_REQUIRE(s > 0 && t > 0 && s % 2 == 0 && t % 2 == 0 && s % t == 0, RF_E_INVALID, "rf_attn_blend: edges s=%d t=%d must be even and t | s", s, t);
     const size_t total = (size_t)b * c * s * s * (s / 2);
-    const size_t want = (total + 255) / 256;
-    hipLaunchKernelGGL(k_attn_blend, dim3((unsigned)(want < 16384 ? want : 16384)), dim3(256), 0, (hipStream_t)stream, x, retrieved, weights,
-                       switches, b, k, c, s, t, out);
-    RF_CHECK_LAUNCH("rf_attn_blend");
-    return RF_OK;
+    return rf_launch<k_attn_blend>("rf_attn_blend", dim3(rf_blocks(total, 256, 16384)), dim3(256), (hipStream_t)stream, x, retrieved, weights, switches, b, k, c, s, t,
+                                   out);
 }

@@ -27,7 +27,7 @@ void rf_set_error(const char* fmt, ...);
     } while (0)
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a PER-DEVICE attribute of a kernel: a process that drives several GPUs has to
-// opt in on each of them.  One instance per kernel instantiation (function-local static); bit d = "done on device d".
+// opt in on each of them.  One instance per kernel instantiation (the function-local static of rf_launch below, its only user); bit d = "done on device d".
 #include <atomic>
 struct RfLdsOptIn {
     std::atomic<unsigned long long> done[4];
@@ -44,18 +44,38 @@ struct RfLdsOptIn {
     }
 };
 
-// The tail of a launcher: opt in where the kernel instantiation KERN ever asks for more than the 64 KB of dynamic LDS a kernel gets without asking
-// (`lds_limit` = the most it asks for; `lds` = this launch's), launch, check.  `who`: the entry point the caller serves, for the error texts.
+// The tail of EVERY launcher (the only caller of hipLaunchKernelGGL and the only user of RfLdsOptIn): opt in where the kernel instantiation KERN ever
+// asks for more than the 64 KB of dynamic LDS a kernel gets without asking, launch, check.  `lds` = this launch's bytes; `lds_limit` = the most the
+// INSTANTIATION asks for, a compile-time or file-scope constant (T::LDS_BYTES, VL_LDS_MAX, ...) and never this call's `lds`: the opt-in is made once per
+// device, so a limit taken from the first call would be too low for a later, larger one.  `who`: the entry point the caller serves, for the error texts.
+// An entry point that launches more than once writes `if (int rc = rf_launch<...>(...)) return rc;` for all but its last launch.
 template <auto KERN, class... Args>
-static inline int rf_launch(const char* who, dim3 grid, size_t lds, size_t lds_limit, hipStream_t stream, Args... args) {
+static inline int rf_launch(const char* who, dim3 grid, dim3 block, size_t lds, size_t lds_limit, hipStream_t stream, Args... args) {
     if (lds_limit > 64 * 1024) {
         static RfLdsOptIn opt;
         if (int rc = opt.ensure(reinterpret_cast<const void*>(KERN), (int)lds_limit, who)) return rc;
     }
-    hipLaunchKernelGGL(KERN, grid, dim3(512), lds, stream, args...);
+    hipLaunchKernelGGL(KERN, grid, block, lds, stream, args...);
     RF_CHECK_LAUNCH(who);
     return RF_OK;
 }
+// ... of a kernel without dynamic LDS
+template <auto KERN, class... Args>
+static inline int rf_launch(const char* who, dim3 grid, dim3 block, hipStream_t stream, Args... args) {
+    hipLaunchKernelGGL(KERN, grid, block, 0, stream, args...);
+    RF_CHECK_LAUNCH(who);
+    return RF_OK;
+}
+
+// Blocks of a capped grid-stride launch: ceil(total / per_block), at most `cap`.
+static inline unsigned rf_blocks(size_t total, size_t per_block, size_t cap) {
+    const size_t want = (total + per_block - 1) / per_block;
+    return (unsigned)(want < cap ? want : cap);
+}
+
+// out[i] = (float)(sum over g = 0..slices-1, in that order, of (double)parts[g * count + i]): the end of every split-K weight gradient whose slices
+// are plain fp32 partials (rf_conv3d_k3_wgrad, rf_conv3d_valid_wgrad, rf_linear_wgrad).  Deterministic, no atomics.  Defined in conv3d_backward.hip.
+int rf_slice_sum(const float* parts, int slices, size_t count, float* out, hipStream_t stream, const char* who);
 
 static inline bool rf_is_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
 static inline int rf_ilog2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }

@@ -37,11 +37,8 @@ extern "C" size_t rf_conv3_packed_floats(int cout, int cin) {
 extern "C" int rf_conv3_pack_weight(const float* w, int cout, int cin, float* wp, void* stream) {
     RF_REQUIRE(w && wp && cout > 0 && cin > 0, RF_E_INVALID, "rf_conv3_pack_weight: bad arguments");
     const size_t total = rf_conv3_packed_floats(cout, cin);
-    const int blocks = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
-    hipLaunchKernelGGL(k_conv3_pack, dim3(blocks), dim3(256), 0, (hipStream_t)stream, w, cout, cin,
-                       rf_round_up(cin, 4), rf_round_up(cout, 16), wp);
-    RF_CHECK_LAUNCH("rf_conv3_pack_weight");
-    return RF_OK;
+    return rf_launch<k_conv3_pack>("rf_conv3_pack_weight", dim3(rf_blocks(total, 256, 2048)), dim3(256), (hipStream_t)stream, w, cout, cin, rf_round_up(cin, 4),
+                                   rf_round_up(cout, 16), wp);
 }
 
 // ------------------------------------------------------------------------------------------- GroupNorm stats
@@ -139,13 +136,11 @@ extern "C" int rf_gn_stats(const float* src0, int c0, const float* src1, int c1,
     const size_t vol0 = (size_t)edge * edge * edge, vol1 = vol0 / 8;
     const int cpg = C / groups;
     const int slices = gn_slices((size_t)cpg * vol0);
-    hipLaunchKernelGGL(k_gn_partial, dim3(n * groups, slices), dim3(256), 0, (hipStream_t)stream, src0, c0, src1, c1, vol0, vol1,
-                       groups, cpg, slices, (double2*)ws);
-    RF_CHECK_LAUNCH("rf_gn_stats(partial)");
-    hipLaunchKernelGGL(k_gn_finalize, dim3((n * C + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const double2*)ws, n, C, groups, cpg,
-                       slices, (double)cpg * (double)vol0, gamma, beta, (double)eps, reinterpret_cast<float4*>(gn_affine));
-    RF_CHECK_LAUNCH("rf_gn_stats(finalize)");
-    return RF_OK;
+    if (int rc = rf_launch<k_gn_partial>("rf_gn_stats(partial)", dim3(n * groups, slices), dim3(256), (hipStream_t)stream, src0, c0, src1, c1, vol0, vol1, groups, cpg,
+                                         slices, (double2*)ws))
+        return rc;
+    return rf_launch<k_gn_finalize>("rf_gn_stats(finalize)", dim3((n * C + 255) / 256), dim3(256), (hipStream_t)stream, (const double2*)ws, n, C, groups, cpg, slices,
+                                    (double)cpg * (double)vol0, gamma, beta, (double)eps, reinterpret_cast<float4*>(gn_affine));
 }
 
 static int conv_check(const char* who, const float* src0, int c0, const float* src1, int c1, int n, int edge, const float* gn_affine,
@@ -199,12 +194,8 @@ extern "C" int rf_conv3d_k3_gn_relu_direct(const float* src0, int c0, const floa
     int rc = conv_check("rf_conv3d_k3_gn_relu_direct", src0, c0, src1, c1, n, edge, gn_affine, w_oidhw, cout, out);
     if (rc) return rc;
     const size_t total = (size_t)n * cout * edge * edge * edge;
-    const size_t want = (total + 255) / 256;
-    const int blocks = (int)(want < 8192 ? want : 8192);
-    hipLaunchKernelGGL(k_conv3_direct, dim3(blocks), dim3(256), 0, (hipStream_t)stream, src0, c0, src1, c1, n, edge, reinterpret_cast<const float4*>(gn_affine),
-                       w_oidhw, cout, out);
-    RF_CHECK_LAUNCH("rf_conv3d_k3_gn_relu_direct");
-    return RF_OK;
+    return rf_launch<k_conv3_direct>("rf_conv3d_k3_gn_relu_direct", dim3(rf_blocks(total, 256, 8192)), dim3(256), (hipStream_t)stream, src0, c0, src1, c1, n, edge,
+                                     reinterpret_cast<const float4*>(gn_affine), w_oidhw, cout, out);
 }
 
 // --------------------------------------------------------------------------------------------------- max pool
@@ -293,18 +284,14 @@ static int maxpool_impl(const float* x, int n, int c, int edge, float* out, doub
         const size_t planes = (size_t)n * c, ov = (size_t)(edge / 2) * (edge / 2) * (edge / 2);
         const unsigned blocks = (unsigned)((planes * ov + 255) / 256);
         double2* st = reinterpret_cast<double2*>(stats);
-        if (edge == 2) hipLaunchKernelGGL(k_maxpool2_small<1>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, planes, out, st);
-        else if (edge == 4) hipLaunchKernelGGL(k_maxpool2_small<8>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, planes, out, st);
-        else hipLaunchKernelGGL(k_maxpool2_small<64>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, planes, out, st);
-        RF_CHECK_LAUNCH("rf_maxpool3d_2");
-        return RF_OK;
+        if (edge == 2) return rf_launch<k_maxpool2_small<1>>("rf_maxpool3d_2", dim3(blocks), dim3(256), (hipStream_t)stream, x, planes, out, st);
+        if (edge == 4) return rf_launch<k_maxpool2_small<8>>("rf_maxpool3d_2", dim3(blocks), dim3(256), (hipStream_t)stream, x, planes, out, st);
+        return rf_launch<k_maxpool2_small<64>>("rf_maxpool3d_2", dim3(blocks), dim3(256), (hipStream_t)stream, x, planes, out, st);
     }
     const int chunks = rf_maxpool_stats_tiles(edge);
     const size_t units = (size_t)n * c * chunks;
-    hipLaunchKernelGGL(k_maxpool2, dim3((unsigned)((units + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, units, edge, chunks, out,
-                       reinterpret_cast<double2*>(stats));
-    RF_CHECK_LAUNCH("rf_maxpool3d_2");
-    return RF_OK;
+    return rf_launch<k_maxpool2>("rf_maxpool3d_2", dim3((unsigned)((units + 3) / 4)), dim3(256), (hipStream_t)stream, x, units, edge, chunks, out,
+                                 reinterpret_cast<double2*>(stats));
 }
 
 extern "C" int rf_maxpool3d_2(const float* x, int n, int c, int edge, float* out, void* stream) {
@@ -368,15 +355,12 @@ extern "C" int rf_gn_from_stats(const double* stats0, int c0, int tiles0, const 
     const int units = n * groups;
     const long long entries = (long long)cpg * (tiles0 > tiles1 ? tiles0 : tiles1);     // stats entries one unit sums (upper bound)
     if (entries <= 128 && units >= 1024)
-        hipLaunchKernelGGL(k_gn_from_stats<1>, dim3((units + 255) / 256), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const double2*>(stats0), c0,
-                           tiles0, reinterpret_cast<const double2*>(stats1), c1, tiles1, units, groups, cpg, (double)cpg * edge * edge * edge, gamma,
-                           beta, (double)eps, reinterpret_cast<float4*>(gn_affine));
-    else
-        hipLaunchKernelGGL(k_gn_from_stats<64>, dim3((units + 3) / 4), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const double2*>(stats0), c0,
-                           tiles0, reinterpret_cast<const double2*>(stats1), c1, tiles1, units, groups, cpg, (double)cpg * edge * edge * edge, gamma,
-                           beta, (double)eps, reinterpret_cast<float4*>(gn_affine));
-    RF_CHECK_LAUNCH("rf_gn_from_stats");
-    return RF_OK;
+        return rf_launch<k_gn_from_stats<1>>("rf_gn_from_stats", dim3((units + 255) / 256), dim3(256), (hipStream_t)stream, reinterpret_cast<const double2*>(stats0), c0,
+                                             tiles0, reinterpret_cast<const double2*>(stats1), c1, tiles1, units, groups, cpg, (double)cpg * edge * edge * edge,
+                                             gamma, beta, (double)eps, reinterpret_cast<float4*>(gn_affine));
+    return rf_launch<k_gn_from_stats<64>>("rf_gn_from_stats", dim3((units + 3) / 4), dim3(256), (hipStream_t)stream, reinterpret_cast<const double2*>(stats0), c0, tiles0,
+                                          reinterpret_cast<const double2*>(stats1), c1, tiles1, units, groups, cpg, (double)cpg * edge * edge * edge, gamma, beta,
+                                          (double)eps, reinterpret_cast<float4*>(gn_affine));
 }
 
 // ------------------------------------------------------------------------------------------ 1x1x1 conv + tanh
@@ -404,11 +388,8 @@ extern "C" int rf_conv1x1_tanh(const float* x, int n, int c, size_t voxels, cons
                                float post_add, float post_mul, float* out, void* stream) {
     RF_REQUIRE(x && w && b && out && n > 0 && c > 0 && voxels > 0, RF_E_INVALID, "rf_conv1x1_tanh: bad arguments");
     RF_REQUIRE((voxels & 3) == 0, RF_E_UNSUPPORTED, "rf_conv1x1_tanh: voxel count must be a multiple of 4");
-    const size_t want = ((size_t)n * (voxels / 4) + 255) / 256;
-    hipLaunchKernelGGL(k_conv1x1_tanh, dim3((unsigned)(want < 4096 ? want : 4096)), dim3(256), 0, (hipStream_t)stream, x, n, c, voxels, w, b,
-                       post_add, post_mul, out);
-    RF_CHECK_LAUNCH("rf_conv1x1_tanh");
-    return RF_OK;
+    return rf_launch<k_conv1x1_tanh>("rf_conv1x1_tanh", dim3(rf_blocks((size_t)n * (voxels / 4), 256, 4096)), dim3(256), (hipStream_t)stream, x, n, c, voxels, w, b,
+                                     post_add, post_mul, out);
 }
 
 // ------------------------------------------------------------------------------- valid strided conv + LeakyReLU
@@ -443,9 +424,6 @@ extern "C" int rf_conv3d_valid_leaky(const float* x, int n, int cin, int s, cons
     RF_REQUIRE(x && w && out && n > 0 && cin > 0 && cout > 0 && k > 0 && stride > 0 && s >= k, RF_E_INVALID, "rf_conv3d_valid_leaky: bad arguments");
     const int so = (s - k) / stride + 1;
     const size_t total = (size_t)n * cout * so * so * so;
-    const size_t want = (total + 255) / 256;
-    hipLaunchKernelGGL(k_conv3_valid, dim3((unsigned)(want < 16384 ? want : 16384)), dim3(256), 0, (hipStream_t)stream, x, n, cin, s, w, bias,
-                       cout, k, stride, slope, so, out);
-    RF_CHECK_LAUNCH("rf_conv3d_valid_leaky");
-    return RF_OK;
+    return rf_launch<k_conv3_valid>("rf_conv3d_valid_leaky", dim3(rf_blocks(total, 256, 16384)), dim3(256), (hipStream_t)stream, x, n, cin, s, w, bias, cout, k, stride,
+                                    slope, so, out);
 }

@@ -21,11 +21,8 @@ __global__ __launch_bounds__(256) void k_relu_bwd(const float4* __restrict__ dy,
 
 extern "C" int rf_relu_backward(const float* dy, const float* y, size_t count, float* out, void* stream) {
     RF_REQUIRE(dy && y && out && count > 0 && (count & 3) == 0, RF_E_INVALID, "rf_relu_backward: bad arguments (count must be a multiple of 4)");
-    const size_t want = (count / 4 + 255) / 256;
-    hipLaunchKernelGGL(k_relu_bwd, dim3((unsigned)(want < 16384 ? want : 16384)), dim3(256), 0, (hipStream_t)stream, (const float4*)dy, (const float4*)y,
-                       count / 4, (float4*)out);
-    RF_CHECK_LAUNCH("rf_relu_backward");
-    return RF_OK;
+    return rf_launch<k_relu_bwd>("rf_relu_backward", dim3(rf_blocks(count / 4, 256, 16384)), dim3(256), (hipStream_t)stream, (const float4*)dy, (const float4*)y,
+                                 count / 4, (float4*)out);
 }
 
 // The same mask, and max |out| beside it: workgroup b leaves its maximum in slot b of RF_AMAX_SLOTS floats (and zeroes the slots b + gridDim.x, ...
@@ -62,11 +59,8 @@ extern "C" int rf_relu_backward_amax_slots(void) { return RF_AMAX_SLOTS; }
 
 extern "C" int rf_relu_backward_amax(const float* dy, const float* y, size_t count, float* out, float* amax_slots, void* stream) {
     RF_REQUIRE(dy && y && out && amax_slots && count > 0 && (count & 3) == 0, RF_E_INVALID, "rf_relu_backward_amax: bad arguments (count must be a multiple of 4)");
-    const size_t want = (count / 4 + 255) / 256;
-    hipLaunchKernelGGL(k_relu_bwd_amax, dim3((unsigned)(want < (size_t)RF_AMAX_SLOTS ? want : (size_t)RF_AMAX_SLOTS)), dim3(256), 0, (hipStream_t)stream,
-                       (const float4*)dy, (const float4*)y, count / 4, (float4*)out, amax_slots);
-    RF_CHECK_LAUNCH("rf_relu_backward_amax");
-    return RF_OK;
+    return rf_launch<k_relu_bwd_amax>("rf_relu_backward_amax", dim3(rf_blocks(count / 4, 256, RF_AMAX_SLOTS)), dim3(256), (hipStream_t)stream, (const float4*)dy,
+                                      (const float4*)y, count / 4, (float4*)out, amax_slots);
 }
 
 // identity GroupNorm affine (mean 0, shift 0) with scale s = the power of two that puts max |dz| into [512, 1024): rows x (0, s, 0, 0), and
@@ -96,9 +90,8 @@ __global__ __launch_bounds__(256) void k_dgrad_affine(const float* __restrict__ 
 
 extern "C" int rf_dgrad_scale_affine(const float* amax_slots, int rows, float* affine, float* scales, void* stream) {
     RF_REQUIRE(amax_slots && affine && scales && rows > 0, RF_E_INVALID, "rf_dgrad_scale_affine: bad arguments");
-    hipLaunchKernelGGL(k_dgrad_affine, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream, amax_slots, rows, reinterpret_cast<float4*>(affine), scales);
-    RF_CHECK_LAUNCH("rf_dgrad_scale_affine");
-    return RF_OK;
+    return rf_launch<k_dgrad_affine>("rf_dgrad_scale_affine", dim3((unsigned)((rows + 255) / 256)), dim3(256), (hipStream_t)stream, amax_slots, rows,
+                                     reinterpret_cast<float4*>(affine), scales);
 }
 
 // ------------------------------------------------------------------------------------- pooling / upsampling of the training slice
@@ -131,10 +124,8 @@ __global__ __launch_bounds__(256) void k_maxpool2_bwd(const float* __restrict__ 
 extern "C" int rf_maxpool3d_2_backward(const float* x, const float* dy, int n, int c, int edge, float* dx, void* stream) {
     RF_REQUIRE(x && dy && dx && n > 0 && c > 0 && edge >= 2 && edge % 2 == 0, RF_E_INVALID, "rf_maxpool3d_2_backward: bad arguments");
     const int half = edge / 2;
-    const size_t cells = (size_t)n * c * half * half * half, want = (cells + 255) / 256;
-    hipLaunchKernelGGL(k_maxpool2_bwd, dim3((unsigned)(want < 65536 ? want : 65536)), dim3(256), 0, (hipStream_t)stream, x, dy, cells, half, dx);
-    RF_CHECK_LAUNCH("rf_maxpool3d_2_backward");
-    return RF_OK;
+    const size_t cells = (size_t)n * c * half * half * half;
+    return rf_launch<k_maxpool2_bwd>("rf_maxpool3d_2_backward", dim3(rf_blocks(cells, 256, 65536)), dim3(256), (hipStream_t)stream, x, dy, cells, half, dx);
 }
 
 // nearest-neighbour x2 upsample (reference model/unet.py:297-308: F.interpolate(scale_factor = 2) ahead of a decoder's concat) and its backward, the sum
@@ -155,10 +146,8 @@ __global__ __launch_bounds__(256) void k_upsample2(const float* __restrict__ lo,
 
 extern "C" int rf_upsample3d_2(const float* lo, int n, int c, int edge_lo, float* hi, void* stream) {
     RF_REQUIRE(lo && hi && n > 0 && c > 0 && edge_lo >= 2 && edge_lo % 2 == 0, RF_E_INVALID, "rf_upsample3d_2: bad arguments (even low-resolution edge)");
-    const size_t pairs = (size_t)n * c * edge_lo * edge_lo * (edge_lo / 2), want = (pairs + 255) / 256;
-    hipLaunchKernelGGL(k_upsample2, dim3((unsigned)(want < 65536 ? want : 65536)), dim3(256), 0, (hipStream_t)stream, lo, pairs, edge_lo, hi);
-    RF_CHECK_LAUNCH("rf_upsample3d_2");
-    return RF_OK;
+    const size_t pairs = (size_t)n * c * edge_lo * edge_lo * (edge_lo / 2);
+    return rf_launch<k_upsample2>("rf_upsample3d_2", dim3(rf_blocks(pairs, 256, 65536)), dim3(256), (hipStream_t)stream, lo, pairs, edge_lo, hi);
 }
 
 __global__ __launch_bounds__(256) void k_sumpool2(const float* __restrict__ hi, size_t cells, int half, float* __restrict__ lo) {
@@ -181,10 +170,8 @@ __global__ __launch_bounds__(256) void k_sumpool2(const float* __restrict__ hi, 
 extern "C" int rf_sumpool3d_2(const float* hi, int n, int c, int edge, float* lo, void* stream) {
     RF_REQUIRE(hi && lo && n > 0 && c > 0 && edge >= 2 && edge % 2 == 0, RF_E_INVALID, "rf_sumpool3d_2: bad arguments");
     const int half = edge / 2;
-    const size_t cells = (size_t)n * c * half * half * half, want = (cells + 255) / 256;
-    hipLaunchKernelGGL(k_sumpool2, dim3((unsigned)(want < 65536 ? want : 65536)), dim3(256), 0, (hipStream_t)stream, hi, cells, half, lo);
-    RF_CHECK_LAUNCH("rf_sumpool3d_2");
-    return RF_OK;
+    const size_t cells = (size_t)n * c * half * half * half;
+    return rf_launch<k_sumpool2>("rf_sumpool3d_2", dim3(rf_blocks(cells, 256, 65536)), dim3(256), (hipStream_t)stream, hi, cells, half, lo);
 }
 
 // ------------------------------------------------------------------------------------------- GroupNorm backward
@@ -389,16 +376,14 @@ extern "C" int rf_gn_backward(const float* x, const float* dxn, int n, int c, in
     int L = 1;
     while (L < 256 && (size_t)L < units) L <<= 1;                   // lanes per row: the power of two >= its units, at most a workgroup
     const int rows = n * c, rpw = 256 / L;
-    hipLaunchKernelGGL(k_gnb_partial, dim3((unsigned)((rows + rpw - 1) / rpw), P), dim3(256), 0, s, x, dxn, vol, P, L, rows, part);
-    RF_CHECK_LAUNCH("rf_gn_backward(partial)");
-    hipLaunchKernelGGL(k_gnb_finalize, dim3(n * groups), dim3(64), 0, s, part, gamma, c, cpg, vol, P, (double)eps, dxn_inv_scale, moments, coef, a1, a2);
-    RF_CHECK_LAUNCH("rf_gn_backward(finalize)");
-    const size_t want = ((size_t)rows * units + 255) / 256;
-    hipLaunchKernelGGL(k_gnb_apply, dim3((unsigned)(want < 65536 ? want : 65536)), dim3(256), 0, s, x, dxn, vol, (size_t)rows, moments, coef, dx);
-    RF_CHECK_LAUNCH("rf_gn_backward(apply)");
-    hipLaunchKernelGGL(k_gnb_sum_n, dim3(c), dim3(64), 0, s, a1, a2, n, c, dxn_inv_scale, dgamma, dbeta);
-    RF_CHECK_LAUNCH("rf_gn_backward(sum)");
-    return RF_OK;
+    if (int rc = rf_launch<k_gnb_partial>("rf_gn_backward(partial)", dim3((unsigned)((rows + rpw - 1) / rpw), P), dim3(256), s, x, dxn, vol, P, L, rows, part)) return rc;
+    if (int rc = rf_launch<k_gnb_finalize>("rf_gn_backward(finalize)", dim3(n * groups), dim3(64), s, part, gamma, c, cpg, vol, P, (double)eps, dxn_inv_scale, moments, coef,
+                                           a1, a2))
+        return rc;
+    if (int rc = rf_launch<k_gnb_apply>("rf_gn_backward(apply)", dim3(rf_blocks((size_t)rows * units, 256, 65536)), dim3(256), s, x, dxn, vol, (size_t)rows, moments, coef,
+                                        dx))
+        return rc;
+    return rf_launch<k_gnb_sum_n>("rf_gn_backward(sum)", dim3(c), dim3(64), s, a1, a2, n, c, dxn_inv_scale, dgamma, dbeta);
 }
 
 // ------------------------------------------------------------------------------------------------- weight gradient
@@ -495,12 +480,18 @@ __global__ __launch_bounds__(512) void k_conv3_wgrad(WgradArgs a) {
     }
 }
 
-__global__ __launch_bounds__(256) void k_wgrad_reduce(const float* __restrict__ parts, int gb, size_t count, float* __restrict__ dw) {
+// THE float64 slice-order sum of split-K partials (common.h:rf_slice_sum): out[i] = (float)(parts[i] + parts[count + i] + ... in float64), rounded once.
+// This convolution's, the valid convolution's and the Linear layer's weight gradients end here.  (k_wgrad_split_reduce, conv3d_wgrad_split.hip, is another sum.)
+__global__ __launch_bounds__(256) void k_slice_sum(const float* __restrict__ parts, int slices, size_t count, float* __restrict__ out) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (size_t)gridDim.x * blockDim.x) {
         double s = 0.0;
-        for (int g = 0; g < gb; ++g) s += (double)parts[(size_t)g * count + i];
-        dw[i] = (float)s;
+        for (int g = 0; g < slices; ++g) s += (double)parts[(size_t)g * count + i];
+        out[i] = (float)s;
     }
+}
+
+int rf_slice_sum(const float* parts, int slices, size_t count, float* out, hipStream_t stream, const char* who) {
+    return rf_launch<k_slice_sum>(who, dim3((unsigned)((count + 255) / 256)), dim3(256), stream, parts, slices, count, out);
 }
 
 static int wgrad_groups(int n, int edge) {
@@ -522,11 +513,10 @@ extern "C" int rf_conv3d_k3_wgrad(const float* x, int cin, int n, int edge, cons
     a.x = x; a.affine = reinterpret_cast<const float4*>(gn_affine); a.dz = dz; a.parts = (float*)ws;
     a.cin = cin; a.cout = cout; a.n = n; a.edge = edge; a.gb = wgrad_groups(n, edge);
     hipStream_t s = (hipStream_t)stream;
-    if (edge == 4) hipLaunchKernelGGL(k_conv3_wgrad<true>, dim3((cin + 3) / 4, (cout + 15) / 16, a.gb), dim3(512), 0, s, a);
-    else hipLaunchKernelGGL(k_conv3_wgrad<false>, dim3((cin + 3) / 4, (cout + 15) / 16, a.gb), dim3(512), 0, s, a);
-    RF_CHECK_LAUNCH("rf_conv3d_k3_wgrad");
-    const size_t count = (size_t)cout * cin * 27;
-    hipLaunchKernelGGL(k_wgrad_reduce, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, (const float*)ws, a.gb, count, dw);
-    RF_CHECK_LAUNCH("rf_conv3d_k3_wgrad(reduce)");
-    return RF_OK;
+    const dim3 grid((cin + 3) / 4, (cout + 15) / 16, a.gb);
+    const char* who = "rf_conv3d_k3_wgrad";
+    if (int rc = edge == 4 ? rf_launch<k_conv3_wgrad<true>>(who, grid, dim3(512), s, a)
+                           : rf_launch<k_conv3_wgrad<false>>(who, grid, dim3(512), s, a))
+        return rc;
+    return rf_slice_sum((const float*)ws, a.gb, (size_t)cout * cin * 27, dw, s, "rf_conv3d_k3_wgrad(reduce)");
 }

@@ -66,11 +66,9 @@ __global__ void k_conv3_e2_split_pack(const float* __restrict__ w, int cout, int
 
 extern "C" int rf_conv3_e2_split_pack_weight(const float* w_oidhw, int cout, int cin, int edge, void* w_packed, void* stream) {
     RF_REQUIRE(w_oidhw && w_packed && cout > 0 && cin > 0 && (edge == 1 || edge == 2), RF_E_INVALID, "rf_conv3_e2_split_pack_weight: bad arguments");
-    const size_t total = rf_conv3_e2_split_packed_bytes(cout, cin, edge) / 16, want = (total + 255) / 256;
-    hipLaunchKernelGGL(k_conv3_e2_split_pack, dim3((unsigned)(want < 4096 ? want : 4096)), dim3(256), 0, (hipStream_t)stream, w_oidhw, cout, cin, edge,
-                       reinterpret_cast<h8*>(w_packed), total);
-    RF_CHECK_LAUNCH("rf_conv3_e2_split_pack_weight");
-    return RF_OK;
+    const size_t total = rf_conv3_e2_split_packed_bytes(cout, cin, edge) / 16;
+    return rf_launch<k_conv3_e2_split_pack>("rf_conv3_e2_split_pack_weight", dim3(rf_blocks(total, 256, 4096)), dim3(256), (hipStream_t)stream, w_oidhw, cout, cin, edge,
+                                            reinterpret_cast<h8*>(w_packed), total);
 }
 
 struct E2Args {
@@ -232,16 +230,11 @@ extern "C" int rf_conv3d_e2_split_k3_gn_relu(const float* src, int cin, int n, i
     const unsigned chunks = (unsigned)e2_chunks(cout, edge);
     const bool wide = (long long)((n + 63) / 64) * chunks >= rf_persistent_wgs() / RF_PERSIST_ROUNDS;
     const dim3 grid((unsigned)((n + (wide ? 63 : 31)) / (wide ? 64 : 32)), chunks);
-    static RfLdsOptIn opt[4];
-    auto launch = [&](auto kern, int slot) -> int {
-        if (int rc = opt[slot].ensure(reinterpret_cast<const void*>(kern), E2_LDS_BYTES, "rf_conv3d_e2_split_k3_gn_relu")) return rc;
-        hipLaunchKernelGGL(kern, grid, dim3(256), E2_LDS_BYTES, (hipStream_t)stream, a);
-        return RF_OK;
-    };
-    int rc;
-    if (edge == 2) rc = wide ? launch(k_conv3_e2_split<8, 64>, 0) : launch(k_conv3_e2_split<8, 32>, 1);
-    else rc = wide ? launch(k_conv3_e2_split<1, 64>, 2) : launch(k_conv3_e2_split<1, 32>, 3);
-    if (rc != RF_OK) return rc;
-    RF_CHECK_LAUNCH("rf_conv3d_e2_split_k3_gn_relu");
-    return RF_OK;
+    const char* who = "rf_conv3d_e2_split_k3_gn_relu";
+    hipStream_t s = (hipStream_t)stream;
+    if (edge == 2)
+        return wide ? rf_launch<k_conv3_e2_split<8, 64>>(who, grid, dim3(256), E2_LDS_BYTES, E2_LDS_BYTES, s, a)
+                    : rf_launch<k_conv3_e2_split<8, 32>>(who, grid, dim3(256), E2_LDS_BYTES, E2_LDS_BYTES, s, a);
+    return wide ? rf_launch<k_conv3_e2_split<1, 64>>(who, grid, dim3(256), E2_LDS_BYTES, E2_LDS_BYTES, s, a)
+                : rf_launch<k_conv3_e2_split<1, 32>>(who, grid, dim3(256), E2_LDS_BYTES, E2_LDS_BYTES, s, a);
 }

@@ -319,18 +319,11 @@ __global__ __launch_bounds__(NW * 64, WPS) void k_conv3_mfma(ConvArgs a) {
 template <int TZ, int TY, int TX, int SPW, int NW, int MB, int NB, int WPS, int CCT = 4>
 static int launch_conv3(const ConvArgs& a, hipStream_t stream) {
     using T = ConvTile<TZ, TY, TX, SPW, NW, MB, NB, CCT>;
-    auto kern = k_conv3_mfma<TZ, TY, TX, SPW, NW, MB, NB, WPS, true, CCT>;
-    if (T::LDS_BYTES > 65536) {
-        static RfLdsOptIn opt_in;
-        if (int rc = opt_in.ensure(reinterpret_cast<const void*>(kern), (int)T::LDS_BYTES, "rf_conv3d_k3_gn_relu")) return rc;
-    }
     unsigned gx;
     if (SPW == 1) gx = (unsigned)a.n * (a.edge / TZ) * (a.edge / TY) * (a.edge / TX);
     else gx = (unsigned)((a.n + SPW - 1) / SPW);
     const unsigned gy = (unsigned)((a.cout16 + T::NCO - 1) / T::NCO);
-    hipLaunchKernelGGL(kern, dim3(gx, gy), dim3(T::NT), T::LDS_BYTES, stream, a);
-    RF_CHECK_LAUNCH("rf_conv3d_k3_gn_relu");
-    return RF_OK;
+    return rf_launch<k_conv3_mfma<TZ, TY, TX, SPW, NW, MB, NB, WPS, true, CCT>>("rf_conv3d_k3_gn_relu", dim3(gx, gy), dim3(T::NT), T::LDS_BYTES, T::LDS_BYTES, stream, a);
 }
 
 // big: 8 waves x MB 4 = 512 voxels (two workgroups = 4 waves/SIMD per CU); small: 4 waves x MB 2 = 128 voxels
@@ -497,9 +490,7 @@ __global__ __launch_bounds__(256) void k_conv3_cin1(ConvArgs a) {
 template <int COUT>
 static int launch_cin1(const ConvArgs& a, hipStream_t stream) {      // edge >= 16
     const unsigned g = (unsigned)a.n * (a.edge / 4) * (a.edge / 16) * (a.edge / 16);
-    hipLaunchKernelGGL((k_conv3_cin1<4, 16, 16, COUT>), dim3(g), dim3(256), 0, stream, a);
-    RF_CHECK_LAUNCH("rf_conv3d_k3_gn_relu(cin1)");
-    return RF_OK;
+    return rf_launch<k_conv3_cin1<4, 16, 16, COUT>>("rf_conv3d_k3_gn_relu(cin1)", dim3(g), dim3(256), stream, a);
 }
 
 // which tiling will rf_conv3d_k3_gn_relu use, and how many stats tiles per sample does that give?

@@ -402,15 +402,8 @@ __global__ __launch_bounds__(512, 4) void k_conv3_small(SmallArgs a) {
 template <int E, int NB, bool UP = false>
 static int launch_small(const SmallArgs& a, hipStream_t stream) {
     using T = SmallTile<E, NB, UP>;
-    auto kern = k_conv3_small<E, NB, UP>;
-    if (T::LDS_BYTES > 65536) {
-        static RfLdsOptIn opt_in;
-        if (int rc = opt_in.ensure(reinterpret_cast<const void*>(kern), (int)T::LDS_BYTES, "rf_conv3d_k3_gn_relu(small)")) return rc;
-    }
     const unsigned gx = (unsigned)((a.n + T::SAMPLES - 1) / T::SAMPLES), gy = (unsigned)((a.cout16 + T::NCO - 1) / T::NCO);
-    hipLaunchKernelGGL(kern, dim3(gx, gy), dim3(T::NT), T::LDS_BYTES, stream, a);
-    RF_CHECK_LAUNCH("rf_conv3d_k3_gn_relu(small)");
-    return RF_OK;
+    return rf_launch<k_conv3_small<E, NB, UP>>("rf_conv3d_k3_gn_relu(small)", dim3(gx, gy), dim3(T::NT), T::LDS_BYTES, T::LDS_BYTES, stream, a);
 }
 
 // Takes whole 4^3 / 2^3 volumes with a single (full-resolution) source when there are enough samples to fill the chip.

@@ -58,11 +58,8 @@ __global__ void k_conv3_split_pack(const float* __restrict__ w, int cout, int ci
 extern "C" int rf_conv3_split_pack_weight(const float* w_oidhw, int cout, int cin, void* w_packed, void* stream) {
     RF_REQUIRE(w_oidhw && w_packed && cout > 0 && cin > 0, RF_E_INVALID, "rf_conv3_split_pack_weight: bad arguments");
     const size_t total = rf_conv3_split_packed_bytes(cout, cin) / 16;
-    const size_t want = (total + 255) / 256;
-    hipLaunchKernelGGL(k_conv3_split_pack, dim3((unsigned)(want < 4096 ? want : 4096)), dim3(256), 0, (hipStream_t)stream, w_oidhw, cout, cin,
-                       rf_round_up(cout, 16) / 16, reinterpret_cast<h8*>(w_packed), total);
-    RF_CHECK_LAUNCH("rf_conv3_split_pack_weight");
-    return RF_OK;
+    return rf_launch<k_conv3_split_pack>("rf_conv3_split_pack_weight", dim3(rf_blocks(total, 256, 4096)), dim3(256), (hipStream_t)stream, w_oidhw, cout, cin,
+                                         rf_round_up(cout, 16) / 16, reinterpret_cast<h8*>(w_packed), total);
 }
 
 // ------------------------------------------------------------------------------------------------------------------- kernel
@@ -644,9 +641,7 @@ extern "C" int rf_conv3d_cin1_presplit(const float* src, int n, int edge, const 
     Cin1PreArgs a;
     a.src = src; a.gamma_in = in_gamma; a.beta_in = in_beta; a.eps_in = (double)in_eps; a.wp = w_packed; a.n = n; a.cin4 = 4; a.cout16 = 16;
     a.gamma = next_gamma; a.beta = next_beta; a.cpg = 8 / next_groups; a.eps = (double)eps; a.out = reinterpret_cast<unsigned char*>(out_presplit);
-    hipLaunchKernelGGL(k_conv3_cin1_presplit, dim3((unsigned)n), dim3(512), 0, (hipStream_t)stream, a);
-    RF_CHECK_LAUNCH("rf_conv3d_cin1_presplit");
-    return RF_OK;
+    return rf_launch<k_conv3_cin1_presplit>("rf_conv3d_cin1_presplit", dim3((unsigned)n), dim3(512), (hipStream_t)stream, a);
 }
 
 // -------------------------------------------------------------------------------------------------------------------- host
@@ -669,7 +664,7 @@ template <int NB, int WPS, bool ONE, bool PADC = false, bool PRE = false>
 static int launch_split(const ConvArgs& a, hipStream_t stream, const char* who, const SplitPreOut& po = SplitPreOut{}) {
     constexpr int LDS = ONE ? CS_BUF : CS_LDS_BYTES;                  // two chunk buffers: 66,560 bytes, past the 64 KB a kernel gets without asking
     const unsigned gx = (unsigned)a.n * (a.edge / 8) * (a.edge / 8) * (a.edge / 8);
-    return rf_launch<k_conv3_split<NB, WPS, ONE, PADC, PRE>>(who, dim3(gx, (unsigned)(a.cout16 / (NB * 16))), LDS, LDS, stream, a, po);
+    return rf_launch<k_conv3_split<NB, WPS, ONE, PADC, PRE>>(who, dim3(gx, (unsigned)(a.cout16 / (NB * 16))), dim3(512), LDS, LDS, stream, a, po);
 }
 
 static int split_run(const ConvArgs& a, hipStream_t stream, const char* who) {
@@ -686,10 +681,10 @@ static int split_run(const ConvArgs& a, hipStream_t stream, const char* who) {
         // all couts of a 32 / 64-cout layer in one workgroup (samples staged once; 4^3 levels of the retrieval backbone: 32 -> 32, 32 -> 64, 64 -> 64)
         static_assert(S4_LDS_BYTES <= 64 * 1024, "k_conv3_split_s4 is launched without an LDS opt-in");
         const unsigned gx = (unsigned)((n + 7) / 8), nbt = (unsigned)(a.cout16 / 16);
-        if (nbt % 4 == 0) return rf_launch<k_conv3_split_s4<4>>(who, dim3(gx, nbt / 4), S4_LDS_BYTES, S4_LDS_BYTES, stream, a);
-        if (nbt % 3 == 0) return rf_launch<k_conv3_split_s4<3>>(who, dim3(gx, nbt / 3), S4_LDS_BYTES, S4_LDS_BYTES, stream, a);      // nf = 12: 48 / 96 couts
-        if (nbt % 2 == 0) return rf_launch<k_conv3_split_s4<2>>(who, dim3(gx, nbt / 2), S4_LDS_BYTES, S4_LDS_BYTES, stream, a);
-        return rf_launch<k_conv3_split_s4<1>>(who, dim3(gx, nbt), S4_LDS_BYTES, S4_LDS_BYTES, stream, a);
+        if (nbt % 4 == 0) return rf_launch<k_conv3_split_s4<4>>(who, dim3(gx, nbt / 4), dim3(512), S4_LDS_BYTES, S4_LDS_BYTES, stream, a);
+        if (nbt % 3 == 0) return rf_launch<k_conv3_split_s4<3>>(who, dim3(gx, nbt / 3), dim3(512), S4_LDS_BYTES, S4_LDS_BYTES, stream, a);      // nf = 12: 48 / 96 couts
+        if (nbt % 2 == 0) return rf_launch<k_conv3_split_s4<2>>(who, dim3(gx, nbt / 2), dim3(512), S4_LDS_BYTES, S4_LDS_BYTES, stream, a);
+        return rf_launch<k_conv3_split_s4<1>>(who, dim3(gx, nbt), dim3(512), S4_LDS_BYTES, S4_LDS_BYTES, stream, a);
     }
     if (a.cout16 <= 32 && rf_split_zcm_takes(cin, n, edge, a.cout)) return rf_split_zcm_launch(a, SplitPreOut{}, false, stream, who);
     if (cin % 8) {

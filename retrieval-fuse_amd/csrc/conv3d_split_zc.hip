@@ -654,8 +654,8 @@ int rf_split_zc_launch(const ConvArgs& a, const SplitPreOut& po, hipStream_t str
     const int wgs = a.n < rf_persistent_wgs() ? a.n : rf_persistent_wgs();      // two workgroups per CU, whole samples each
     const int per = (a.n + wgs - 1) / wgs;
     const dim3 grid((unsigned)((a.n + per - 1) / per));
-    if (a.pool_mode != 2) return rf_launch<k_conv3_split_zc<true>>(who, grid, ZC_LDS_BYTES, ZC_LDS_BYTES, stream, a, po, per);
-    return rf_launch<k_conv3_split_zc<false>>(who, grid, ZC_LDS_BYTES, ZC_LDS_BYTES, stream, a, po, per);
+    if (a.pool_mode != 2) return rf_launch<k_conv3_split_zc<true>>(who, grid, dim3(512), ZC_LDS_BYTES, ZC_LDS_BYTES, stream, a, po, per);
+    return rf_launch<k_conv3_split_zc<false>>(who, grid, dim3(512), ZC_LDS_BYTES, ZC_LDS_BYTES, stream, a, po, per);
 }
 
 // multi-chunk persistent form: up to 32 couts (16 per workgroup: the full-output form runs a 17..32-cout layer as two cout blocks on grid.y, each staging
@@ -672,7 +672,7 @@ static int zcm_launch(const ConvArgs& a, const SplitPreOut& po, hipStream_t stre
     const int wgs = rf_persistent_wgs();                              // two workgroups per CU
     const unsigned cob_blocks = (unsigned)(a.cout16 / 16);
     const int per = (int)((boxes * cob_blocks + wgs - 1) / wgs);
-    return rf_launch<k_conv3_split_zcm<PRE, EPI, CH8>>(who, dim3((unsigned)((boxes + per - 1) / per), cob_blocks), ZM_LDS_BYTES, ZM_LDS_BYTES, stream, a, po, per, (int)boxes);
+    return rf_launch<k_conv3_split_zcm<PRE, EPI, CH8>>(who, dim3((unsigned)((boxes + per - 1) / per), cob_blocks), dim3(512), ZM_LDS_BYTES, ZM_LDS_BYTES, stream, a, po, per, (int)boxes);
 }
 
 // pre: the input is a pre-split tensor; po.pw_out set: the pointwise-head epilogue, else the full output (+ a.stats)

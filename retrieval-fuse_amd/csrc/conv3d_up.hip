@@ -76,11 +76,8 @@ __global__ void k_conv3_up_pack(const float* __restrict__ w, int cout, int c0, i
 extern "C" int rf_conv3_up_pack_weight(const float* w_oidhw, int cout, int c0, int c1, float* w_packed, void* stream) {
     RF_REQUIRE(w_oidhw && w_packed && cout > 0 && c0 >= 0 && c1 > 0, RF_E_INVALID, "rf_conv3_up_pack_weight: bad arguments");
     const size_t total = rf_conv3_up_packed_floats(cout, c0, c1);
-    const size_t want = (total + 255) / 256;
-    hipLaunchKernelGGL(k_conv3_up_pack, dim3((unsigned)(want < 2048 ? want : 2048)), dim3(256), 0, (hipStream_t)stream, w_oidhw, cout, c0, c1,
-                       rf_round_up(c0, 4), rf_round_up(c1, 8), rf_round_up(cout, 16), w_packed);
-    RF_CHECK_LAUNCH("rf_conv3_up_pack_weight");
-    return RF_OK;
+    return rf_launch<k_conv3_up_pack>("rf_conv3_up_pack_weight", dim3(rf_blocks(total, 256, 2048)), dim3(256), (hipStream_t)stream, w_oidhw, cout, c0, c1,
+                                      rf_round_up(c0, 4), rf_round_up(c1, 8), rf_round_up(cout, 16), w_packed);
 }
 
 // ---------------------------------------------------------------------------------------------------------- kernel
@@ -120,11 +117,6 @@ __device__ __forceinline__ void rf_rows4_transpose(float& r0, float& r1, float& 
 // lane id from nothing (v_mbcnt): a value the register allocator can recompute instead of keeping threadIdx.x alive -- or spilling it --
 // across the MFMA phases
 __device__ __forceinline__ int rf_lane() { return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
-
-__device__ __forceinline__ unsigned up_xcd_contiguous(unsigned b, unsigned g) {      // see conv3d_mfma.hip
-    const unsigned per = g >> 3, rem = g & 7u, k = b & 7u;
-    return k * per + (k < rem ? k : rem) + (b >> 3);
-}
 
 // Order of a wave's parity lattice, v = mb*16 + i -> (sample, Z, Y, X).  The lattice plane Z is constant inside an m-block
 // (Z = mb): an m-block on the first / last plane then reads only zero padding through its z-border taps.
@@ -190,7 +182,7 @@ __global__ __launch_bounds__(512, 4) void k_conv3_up(UpArgs a) {
     // ---- which box?
     int n0, z0 = 0, y0 = 0, x0 = 0, tile = 0;
     if (SPW == 1) {
-        const unsigned lb = gridDim.y == 1 ? up_xcd_contiguous(blockIdx.x, gridDim.x) : blockIdx.x;
+        const unsigned lb = gridDim.y == 1 ? rf_xcd_contiguous(blockIdx.x, gridDim.x) : blockIdx.x;
         const int tpe = edge / TE;
         int t = (int)lb;
         tile = t % (tpe * tpe * tpe);
@@ -925,16 +917,9 @@ __global__ __launch_bounds__(512, 4) void k_conv3_up(UpArgs a) {
 template <int TE, int SPW, int MB, int NB, bool HALF = false>
 static int launch_up(const UpArgs& a, hipStream_t stream) {
     using T = UpTile<TE, SPW, MB, NB>;
-    auto kern = k_conv3_up<TE, SPW, MB, NB, HALF>;
-    if (T::LDS_BYTES > 65536) {
-        static RfLdsOptIn opt_in;
-        if (int rc = opt_in.ensure(reinterpret_cast<const void*>(kern), (int)T::LDS_BYTES, "rf_conv3d_up_k3_gn_relu")) return rc;
-    }
     const unsigned gx = SPW == 1 ? (unsigned)a.n * (a.edge / TE) * (a.edge / TE) * (a.edge / TE) : (unsigned)((a.n + SPW - 1) / SPW);
     const unsigned gy = (unsigned)((a.cout16 + T::NCO - 1) / T::NCO);
-    hipLaunchKernelGGL(kern, dim3(gx, gy), dim3(T::NT), T::LDS_BYTES, stream, a);
-    RF_CHECK_LAUNCH("rf_conv3d_up_k3_gn_relu");
-    return RF_OK;
+    return rf_launch<k_conv3_up<TE, SPW, MB, NB, HALF>>("rf_conv3d_up_k3_gn_relu", dim3(gx, gy), dim3(T::NT), T::LDS_BYTES, T::LDS_BYTES, stream, a);
 }
 
 template <int TE, int SPW, int MB>

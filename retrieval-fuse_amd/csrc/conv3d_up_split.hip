@@ -98,11 +98,8 @@ extern "C" int rf_conv3_up_split_pack_weight(const float* w_oidhw, int cout, int
     RF_REQUIRE(w_oidhw && w_packed && cout > 0 && c0 >= 0 && c1 > 0 && c0 % 8 == 0 && c1 % 8 == 0, RF_E_INVALID,
                "rf_conv3_up_split_pack_weight: needs c0 and c1 in multiples of 8 (got %d, %d)", c0, c1);
     const size_t total = rf_conv3_up_split_packed_bytes(cout, c0, c1) / 16;
-    const size_t want = (total + 255) / 256;
-    hipLaunchKernelGGL(k_conv3_up_split_pack, dim3((unsigned)(want < 4096 ? want : 4096)), dim3(256), 0, (hipStream_t)stream, w_oidhw, cout, c0, c1,
-                       rf_round_up(cout, 16) / 16, reinterpret_cast<h8*>(w_packed), total);
-    RF_CHECK_LAUNCH("rf_conv3_up_split_pack_weight");
-    return RF_OK;
+    return rf_launch<k_conv3_up_split_pack>("rf_conv3_up_split_pack_weight", dim3(rf_blocks(total, 256, 4096)), dim3(256), (hipStream_t)stream, w_oidhw, cout, c0, c1,
+                                            rf_round_up(cout, 16) / 16, reinterpret_cast<h8*>(w_packed), total);
 }
 
 // ------------------------------------------------------------------------------------------------------------------- kernel
@@ -1509,20 +1506,20 @@ static UpSplitArgs up_split_pre_args(UpSplitArgs a, void* out_presplit, const fl
 
 template <int NB>
 static int launch_up_split(const UpSplitArgs& a, hipStream_t stream, const char* who) {
-    return rf_launch<k_conv3_up_split<NB>>(who, dim3((unsigned)a.n), US_LDS_ALLOC, US_LDS_ALLOC, stream, a);
+    return rf_launch<k_conv3_up_split<NB>>(who, dim3((unsigned)a.n), dim3(512), US_LDS_ALLOC, US_LDS_ALLOC, stream, a);
 }
 
 // the persistent box form: two workgroups per CU (rf_persistent_wgs), each a run of boxes
 template <int NBG, int CGO>
 static int launch_up_split_boxp(const UpSplitArgs& a, int edge, int boxes, hipStream_t stream, const char* who) {
-    return rf_launch<k_conv3_up_split_boxp<NBG, CGO>>(who, dim3((unsigned)rf_persistent_wgs()), UP_LDS_BYTES, UP_LDS_BYTES, stream, a, edge, boxes);
+    return rf_launch<k_conv3_up_split_boxp<NBG, CGO>>(who, dim3((unsigned)rf_persistent_wgs()), dim3(512), UP_LDS_BYTES, UP_LDS_BYTES, stream, a, edge, boxes);
 }
 
 // boxes with a skip source: NB of the weight image's nbt n-blocks per workgroup; LDS = the larger of the epilogue tile and the images (`img` bytes)
 template <int NB>
 static int launch_up_split_boxskip(const UpSplitArgs& a, int edge, unsigned boxes, int nbt, size_t img, hipStream_t stream, const char* who) {
     const size_t tile = (size_t)(NB * 16) * UB_E_STRIDE * 4;
-    return rf_launch<k_conv3_up_split_boxskip<NB>>(who, dim3(boxes, (unsigned)((nbt + NB - 1) / NB)), tile > img ? tile : img, 160 * 1024, stream, a, edge);
+    return rf_launch<k_conv3_up_split_boxskip<NB>>(who, dim3(boxes, (unsigned)((nbt + NB - 1) / NB)), dim3(512), tile > img ? tile : img, 160 * 1024, stream, a, edge);
 }
 
 static int up_split_dispatch(UpSplitArgs& a, int c0, int c1, int n, int edge, int cout, hipStream_t stream, const char* who);
@@ -1538,7 +1535,7 @@ static bool up_split_pp_takes(int c0, int c1, int n, int cout) {
 
 static int launch_up_split_pp(const UpSplitArgs& a, hipStream_t stream, const char* who) {
     const int wgs = (rf_resident_wgs() / 2) * RF_UP_PP_ROUNDS;
-    return rf_launch<k_conv3_up_split_pp>(who, dim3((unsigned)(a.n < wgs ? a.n : wgs)), PP_LDS_ALLOC, PP_LDS_ALLOC, stream, a);
+    return rf_launch<k_conv3_up_split_pp>(who, dim3((unsigned)(a.n < wgs ? a.n : wgs)), dim3(512), PP_LDS_ALLOC, PP_LDS_ALLOC, stream, a);
 }
 
 extern "C" int rf_conv3d_up_split_k3_gn_relu(const float* src0, int c0, const float* src1, int c1, int n, int edge, const float* gn_affine,
@@ -1565,8 +1562,8 @@ static int up_split_dispatch(UpSplitArgs& a, int c0, int c1, int n, int edge, in
         }
         // one n-block: the tile (16 couts) and the images (c1 <= 8 US_MAX_CGB) both stay below what a kernel gets without asking
         static_assert(16 * UB_E_STRIDE * 4 <= 64 * 1024 && US_MAX_CGB * 2 * US_B_PLANE <= 64 * 1024, "k_conv3_up_split_box<1> is launched without an LDS opt-in");
-        if (nbq == 1) return rf_launch<k_conv3_up_split_box<1>>(who, dim3(boxes), lds_bytes, 0, stream, a, edge);
-        return rf_launch<k_conv3_up_split_box<2>>(who, dim3(boxes), lds_bytes, 32 * UB_E_STRIDE * 4, stream, a, edge);
+        if (nbq == 1) return rf_launch<k_conv3_up_split_box<1>>(who, dim3(boxes), dim3(512), lds_bytes, 0, stream, a, edge);
+        return rf_launch<k_conv3_up_split_box<2>>(who, dim3(boxes), dim3(512), lds_bytes, 32 * UB_E_STRIDE * 4, stream, a, edge);
     }
     if (up_split_boxskip_takes(c0, c1, n, edge, cout)) {
         const unsigned boxes = (unsigned)n * (edge / 8) * (edge / 8) * (edge / 8);
@@ -1581,11 +1578,11 @@ static int up_split_dispatch(UpSplitArgs& a, int c0, int c1, int n, int edge, in
         const dim3 wide((unsigned)((n + 7) / 8), 1u);
         // all 64 (48: nf = 12) couts in one workgroup (256 VGPRs, 132 KB LDS, one workgroup per CU -- the shape of the 8^3 kernel): the samples are
         // staged and converted ONCE instead of once per 16-cout block
-        if (nbt == 4) return rf_launch<k_conv3_up_split_s4<4, true>>(who, wide, 4 * 16 * U4_E_STRIDE * 4, 4 * 16 * U4_E_STRIDE * 4, stream, a);
-        if (nbt == 3) return rf_launch<k_conv3_up_split_s4<3, true>>(who, wide, 3 * 16 * U4_E_STRIDE * 4, 3 * 16 * U4_E_STRIDE * 4, stream, a);
+        if (nbt == 4) return rf_launch<k_conv3_up_split_s4<4, true>>(who, wide, dim3(512), 4 * 16 * U4_E_STRIDE * 4, 4 * 16 * U4_E_STRIDE * 4, stream, a);
+        if (nbt == 3) return rf_launch<k_conv3_up_split_s4<3, true>>(who, wide, dim3(512), 3 * 16 * U4_E_STRIDE * 4, 3 * 16 * U4_E_STRIDE * 4, stream, a);
         // 16 couts per workgroup: the 32-cout instance needs more than the 128 VGPRs that four waves per SIMD allow (35-45 spills) and was
         // no faster (629-641 us against 610 on dec0)
-        return rf_launch<k_conv3_up_split_s4<1, true>>(who, dim3((unsigned)((n + 7) / 8), (unsigned)nbt), U4_LDS_BYTES, U4_LDS_BYTES, stream, a);
+        return rf_launch<k_conv3_up_split_s4<1, true>>(who, dim3((unsigned)((n + 7) / 8), (unsigned)nbt), dim3(512), U4_LDS_BYTES, U4_LDS_BYTES, stream, a);
     }
     return rf_round_up(cout, 16) == 48 ? launch_up_split<3>(a, stream, who) : launch_up_split<4>(a, stream, who);
 }

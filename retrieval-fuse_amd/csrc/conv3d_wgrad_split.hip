@@ -218,7 +218,7 @@ __global__ __launch_bounds__(512, 2) void k_conv3_wgrad_split(WgradSplitArgs a) 
 
 // 64 outputs x 4 slices of the groups per workgroup: a thread sums its groups (g = slice, slice + 4, ...) in float64, the four partial sums are then
 // added in slice order -- a fixed order whatever the launch (the first form, one thread per output walking all the groups, ran 27 workgroups for a
-// 16 -> 16 layer and took as long as the MFMA kernel)
+// 16 -> 16 layer and took as long as the MFMA kernel).  Not common.h:rf_slice_sum: four interleaved partial sums and the 16 / s rescale give other bits.
 __global__ __launch_bounds__(256) void k_wgrad_split_reduce(const float* __restrict__ parts, int gb, size_t count, const float* __restrict__ scales,
                                                             float* __restrict__ dw) {
     __shared__ double red[4][64];
@@ -260,23 +260,16 @@ extern "C" int rf_conv3d_k3_wgrad_split(const float* x, int cin, int n, int edge
                "rf_conv3d_k3_wgrad_split: takes cin >= 6 (at least 3/4 of the next multiple of 8; 4^3: of 4), cout >= 8, edge a power of two >= 8 or 8+ whole 4^3 samples (got cin=%d cout=%d n=%d edge=%d)",
                cin, cout, n, edge);
     RF_REQUIRE(ws_bytes >= rf_conv3d_k3_wgrad_split_ws_bytes(cin, cout, n, edge), RF_E_WORKSPACE, "rf_conv3d_k3_wgrad_split: workspace too small");
-    static RfLdsOptIn opt_box, opt_s4;
     WgradSplitArgs a;
     a.x = x; a.affine = reinterpret_cast<const float4*>(gn_affine); a.dz = dz; a.scales = scales; a.parts = (float*)ws;
     a.cin = cin; a.cout = cout; a.n = n; a.edge = edge; a.gb = wgrad_split_groups(cin, cout, n, edge);
     hipStream_t s = (hipStream_t)stream;
     const int nc = ws_nc(edge == 4);
     const dim3 grid((cin + nc - 1) / nc, (cout + 63) / 64, a.gb);
-    if (edge == 4) {
-        if (int rc = opt_s4.ensure(reinterpret_cast<const void*>(k_conv3_wgrad_split<true>), WS_LDS_BYTES, "rf_conv3d_k3_wgrad_split")) return rc;
-        hipLaunchKernelGGL(k_conv3_wgrad_split<true>, grid, dim3(512), WS_LDS_BYTES, s, a);
-    } else {
-        if (int rc = opt_box.ensure(reinterpret_cast<const void*>(k_conv3_wgrad_split<false>), WS_LDS_BYTES, "rf_conv3d_k3_wgrad_split")) return rc;
-        hipLaunchKernelGGL(k_conv3_wgrad_split<false>, grid, dim3(512), WS_LDS_BYTES, s, a);
-    }
-    RF_CHECK_LAUNCH("rf_conv3d_k3_wgrad_split");
+    const char* who = "rf_conv3d_k3_wgrad_split";
+    if (int rc = edge == 4 ? rf_launch<k_conv3_wgrad_split<true>>(who, grid, dim3(512), WS_LDS_BYTES, WS_LDS_BYTES, s, a)
+                           : rf_launch<k_conv3_wgrad_split<false>>(who, grid, dim3(512), WS_LDS_BYTES, WS_LDS_BYTES, s, a))
+        return rc;
     const size_t count = (size_t)cout * cin * 27;
-    hipLaunchKernelGGL(k_wgrad_split_reduce, dim3((unsigned)((count + 63) / 64)), dim3(256), 0, s, (const float*)ws, a.gb, count, scales, dw);
-    RF_CHECK_LAUNCH("rf_conv3d_k3_wgrad_split(reduce)");
-    return RF_OK;
+    return rf_launch<k_wgrad_split_reduce>("rf_conv3d_k3_wgrad_split(reduce)", dim3((unsigned)((count + 63) / 64)), dim3(256), s, (const float*)ws, a.gb, count, scales, dw);
 }

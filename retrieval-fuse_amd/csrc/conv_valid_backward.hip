@@ -58,11 +58,8 @@ extern "C" int rf_conv3d_valid_leaky_backward(const float* dy, const float* y, i
     const size_t vol = (size_t)so * so * so;
     const int G = lrb_groups(n, vol);
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_leaky_bwd, dim3(G, cout), dim3(256), 0, s, dy, y, n, cout, vol, slope, dz, (float*)ws);
-    RF_CHECK_LAUNCH("rf_conv3d_valid_leaky_backward");
-    hipLaunchKernelGGL(k_db_reduce, dim3((cout + 63) / 64), dim3(64), 0, s, (const float*)ws, G, cout, db);
-    RF_CHECK_LAUNCH("rf_conv3d_valid_leaky_backward(db)");
-    return RF_OK;
+    if (int rc = rf_launch<k_leaky_bwd>("rf_conv3d_valid_leaky_backward", dim3(G, cout), dim3(256), s, dy, y, n, cout, vol, slope, dz, (float*)ws)) return rc;
+    return rf_launch<k_db_reduce>("rf_conv3d_valid_leaky_backward(db)", dim3((cout + 63) / 64), dim3(64), s, (const float*)ws, G, cout, db);
 }
 
 // --------------------------------------------------------------------------------------------------- data gradient
@@ -159,15 +156,13 @@ extern "C" int rf_conv3d_valid_dgrad(const float* dz, int n, int cout, int so, c
     a.cin_pad = rf_round_up(cin, 16); a.cout_pad = rf_round_up(cout, 4);
     const int nq = (s + stride - 1) / stride;                      // the largest phase lattice edge
     const int blocks = (nq * nq * nq + 255) / 256;
-    hipLaunchKernelGGL(k_convv_dgrad, dim3(blocks, a.cin_pad / 16, n * stride * stride * stride), dim3(256), 0, (hipStream_t)stream, a);
-    RF_CHECK_LAUNCH("rf_conv3d_valid_dgrad");
-    return RF_OK;
+    return rf_launch<k_convv_dgrad>("rf_conv3d_valid_dgrad", dim3(blocks, a.cin_pad / 16, n * stride * stride * stride), dim3(256), (hipStream_t)stream, a);
 }
 
 // ------------------------------------------------------------------------------------------------- weight gradient
 // GEMM  dW[co][col] = sum_k dz[co][k] * X[k][col],  col = ci * k^3 + tap (the OIDHW order), k = (n, oz, oy, ox).  K is cut into fixed slices of
 // WG_ROWS output rows (n, oz, oy); a workgroup walks the rows of its slice, four ox per MFMA step (lane group kq takes ox = x0 + kq), and writes its
-// fp32 partial tile to parts[slice][co][col]; k_wgrad_sum adds the slices in float64 in slice order.  MFMA f32 16x16x4: A = dz (16 couts x 4 k),
+// fp32 partial tile to parts[slice][co][col]; rf_slice_sum (common.h) adds the slices in float64 in slice order.  MFMA f32 16x16x4: A = dz (16 couts x 4 k),
 // B = x gathered at o * stride + tap (4 k x 16 columns); a wave keeps four column tiles (64 columns) and reuses the dz operand across them.
 // Workgroup = 4 waves = 16 couts x 256 columns.
 constexpr int WG_ROWS = 256;
@@ -231,14 +226,6 @@ __global__ __launch_bounds__(256) void k_convv_wgrad(WgradVArgs a) {
     }
 }
 
-__global__ __launch_bounds__(256) void k_wgrad_sum(const float* __restrict__ parts, int slices, size_t count, float* __restrict__ dw) {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (size_t)gridDim.x * blockDim.x) {
-        double s = 0.0;
-        for (int g = 0; g < slices; ++g) s += (double)parts[(size_t)g * count + i];
-        dw[i] = (float)s;
-    }
-}
-
 static int wgradv_slices(int n, int so) {
     const long rows = (long)n * so * so;
     return (int)((rows + WG_ROWS - 1) / WG_ROWS);
@@ -260,11 +247,6 @@ extern "C" int rf_conv3d_valid_wgrad(const float* x, int n, int cin, int s, cons
     a.n = n; a.cin = cin; a.cout = cout; a.s = s; a.so = so; a.k = k; a.stride = stride;
     a.cols = cin * k * k * k; a.slices = wgradv_slices(n, so);
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_convv_wgrad, dim3(a.slices, (a.cols + 255) / 256, (cout + 15) / 16), dim3(256), 0, st, a);
-    RF_CHECK_LAUNCH("rf_conv3d_valid_wgrad");
-    const size_t count = (size_t)cout * a.cols;
-    const unsigned blocks = (unsigned)((count + 255) / 256);
-    hipLaunchKernelGGL(k_wgrad_sum, dim3(blocks), dim3(256), 0, st, (const float*)ws, a.slices, count, dw);
-    RF_CHECK_LAUNCH("rf_conv3d_valid_wgrad(sum)");
-    return RF_OK;
+    if (int rc = rf_launch<k_convv_wgrad>("rf_conv3d_valid_wgrad", dim3(a.slices, (a.cols + 255) / 256, (cout + 15) / 16), dim3(256), st, a)) return rc;
+    return rf_slice_sum((const float*)ws, a.slices, (size_t)cout * a.cols, dw, st, "rf_conv3d_valid_wgrad(sum)");
 }

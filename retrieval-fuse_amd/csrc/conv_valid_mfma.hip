@@ -32,11 +32,8 @@ extern "C" size_t rf_convv_packed_floats(int cout, int cin, int k) {
 extern "C" int rf_convv_pack_weight(const float* w_oidhw, int cout, int cin, int k, float* w_packed, void* stream) {
     RF_REQUIRE(w_oidhw && w_packed && cout > 0 && cin > 0 && k > 0, RF_E_INVALID, "rf_convv_pack_weight: bad arguments");
     const size_t total = rf_convv_packed_floats(cout, cin, k);
-    const size_t want = (total + 255) / 256;
-    hipLaunchKernelGGL(k_convv_pack, dim3((unsigned)(want < 2048 ? want : 2048)), dim3(256), 0, (hipStream_t)stream, w_oidhw, cout, cin, k * k * k,
-                       rf_round_up(k * k * k * cin, 4), rf_round_up(cout, 16), w_packed);
-    RF_CHECK_LAUNCH("rf_convv_pack_weight");
-    return RF_OK;
+    return rf_launch<k_convv_pack>("rf_convv_pack_weight", dim3(rf_blocks(total, 256, 2048)), dim3(256), (hipStream_t)stream, w_oidhw, cout, cin, k * k * k,
+                                   rf_round_up(k * k * k * cin, 4), rf_round_up(cout, 16), w_packed);
 }
 
 struct ConvVArgs {
@@ -59,8 +56,7 @@ __global__ __launch_bounds__(256) void k_convv_mfma(ConvVArgs a) {
     // 1-D grid, XCD-aware: workgroups go to the 8 XCDs round-robin by id, each XCD with its own L2.  Every input value of a window is
     // re-read k^3 * (cout blocks) times by different workgroups: remap so that XCD k walks whole windows one after the other
     // (voxel blocks fastest, then cout blocks, then windows) and the window's input stays in that one L2.
-    const unsigned total = gridDim.x, per = total >> 3, rem = total & 7u, xk = blockIdx.x & 7u;
-    const unsigned lb = xk * per + (xk < rem ? xk : rem) + (blockIdx.x >> 3);
+    const unsigned lb = rf_xcd_contiguous(blockIdx.x, gridDim.x);
     const unsigned xb = lb % a.gx, zb = (lb / a.gx) % a.gz;
     const int nn = (int)(lb / (a.gx * a.gz));
     const int cob = (int)zb * (NB * 16);
@@ -179,17 +175,13 @@ extern "C" int rf_conv3d_valid_leaky_mfma(const float* x, int n, int cin, int s,
     RF_REQUIRE((long long)cin * s * s * s < (1ll << 31) && ovol < (1ll << 31), RF_E_UNSUPPORTED, "rf_conv3d_valid_leaky_mfma: window too large");
     hipStream_t st = (hipStream_t)stream;
     // 4 waves x MB m-blocks of 16 voxels per workgroup; small outputs take MB = 1 so tiny windows still spread over waves
-    if (a.cout16 <= 16) {
-        a.gz = 1;
-        if (ovol >= 4096) { a.gx = (unsigned)((ovol + 255) / 256); hipLaunchKernelGGL((k_convv_mfma<4, 1>), dim3(a.gx * a.gz * n), dim3(256), 0, st, a); }
-        else { a.gx = (unsigned)((ovol + 63) / 64); hipLaunchKernelGGL((k_convv_mfma<1, 1>), dim3(a.gx * a.gz * n), dim3(256), 0, st, a); }
-    } else {
-        a.gz = (unsigned)((a.cout16 + 31) / 32);
-        if (ovol >= 4096) { a.gx = (unsigned)((ovol + 255) / 256); hipLaunchKernelGGL((k_convv_mfma<4, 2>), dim3(a.gx * a.gz * n), dim3(256), 0, st, a); }
-        else { a.gx = (unsigned)((ovol + 63) / 64); hipLaunchKernelGGL((k_convv_mfma<1, 2>), dim3(a.gx * a.gz * n), dim3(256), 0, st, a); }
-    }
-    RF_CHECK_LAUNCH("rf_conv3d_valid_leaky_mfma");
-    return RF_OK;
+    const bool big = ovol >= 4096;
+    a.gx = (unsigned)(big ? (ovol + 255) / 256 : (ovol + 63) / 64);
+    a.gz = a.cout16 <= 16 ? 1u : (unsigned)((a.cout16 + 31) / 32);
+    const dim3 grid(a.gx * a.gz * n);
+    const char* who = "rf_conv3d_valid_leaky_mfma";
+    if (a.cout16 <= 16) return big ? rf_launch<k_convv_mfma<4, 1>>(who, grid, dim3(256), st, a) : rf_launch<k_convv_mfma<1, 1>>(who, grid, dim3(256), st, a);
+    return big ? rf_launch<k_convv_mfma<4, 2>>(who, grid, dim3(256), st, a) : rf_launch<k_convv_mfma<1, 2>>(who, grid, dim3(256), st, a);
 }
 
 // ====================================================================================================================
@@ -237,11 +229,8 @@ extern "C" size_t rf_convv_lds_packed_floats(int cout, int cin, int k) {
 
 extern "C" int rf_convv_lds_pack_weight(const float* w_oidhw, int cout, int cin, int k, float* w_packed, void* stream) {
     RF_REQUIRE(w_oidhw && w_packed && cout > 0 && cin > 0 && k > 0, RF_E_INVALID, "rf_convv_lds_pack_weight: bad arguments");
-    const size_t want = (rf_convv_lds_packed_floats(cout, cin, k) + 255) / 256;
-    hipLaunchKernelGGL(k_convv_lds_pack, dim3((unsigned)(want < 2048 ? want : 2048)), dim3(256), 0, (hipStream_t)stream, w_oidhw, cout, cin, k * k * k,
-                       (k * k * k + 3) / 4, rf_round_up(cout, 16), w_packed);
-    RF_CHECK_LAUNCH("rf_convv_lds_pack_weight");
-    return RF_OK;
+    return rf_launch<k_convv_lds_pack>("rf_convv_lds_pack_weight", dim3(rf_blocks(rf_convv_lds_packed_floats(cout, cin, k), 256, 2048)), dim3(256), (hipStream_t)stream,
+                                       w_oidhw, cout, cin, k * k * k, (k * k * k + 3) / 4, rf_round_up(cout, 16), w_packed);
 }
 
 #define RF_VL_SEG 24          // staged floats per thread (one segment of one input row)
@@ -259,8 +248,7 @@ __global__ __launch_bounds__(512) void k_convv_lds(ConvVLArgs a) {
     int* toff = reinterpret_cast<int*>(wsl + CC * G * 4 * WS);      // [G * 4]
 
     // XCD-aware 1-D grid as in the gather form: an XCD walks whole windows (tiles fastest, then cout blocks)
-    const unsigned total = gridDim.x, per = total >> 3, rem = total & 7u, xk = blockIdx.x & 7u;
-    const unsigned lb = xk * per + (xk < rem ? xk : rem) + (blockIdx.x >> 3);
+    const unsigned lb = rf_xcd_contiguous(blockIdx.x, gridDim.x);
     const unsigned tiles = (unsigned)(a.ntz * a.nty);
     const unsigned tb = lb % tiles, zb = (lb / tiles) % (unsigned)a.gz;
     const int nn = (int)(lb / (tiles * (unsigned)a.gz));
@@ -435,6 +423,7 @@ __global__ __launch_bounds__(512) void k_convv_lds(ConvVLArgs a) {
 
 // tile choice: (tz, ty) output rows with tz*ty*so <= 512 voxels, <= 512 staged rows per chunk, segments <= RF_VL_SEG floats and
 // the chunk within the LDS budget; among those the one that wastes the fewest MFMA slots (ragged last tiles + unfilled m-blocks)
+constexpr size_t VL_LDS_MAX = 72 * 1024;       // the LDS budget (two workgroups per CU), and so the most any k_convv_lds instantiation asks for: its opt-in limit
 static bool convv_lds_plan(int n, int cin, int s, int cout, int k, int stride, ConvVLArgs& a, int& cc_out, size_t& lds_out) {
     const int so = (s - k) / stride + 1;
     if (so < 8 || k > 5 || s > 64) return false;
@@ -457,7 +446,7 @@ static bool convv_lds_plan(int n, int cin, int s, int cout, int k, int stride, C
             const int ws = nbw * 16 + ((nbw * 16) % 32 == 0 ? 16 : 0);
             size_t lds = ((size_t)CC * ch + (size_t)CC * G * 4 * ws + (size_t)G * 4) * sizeof(float);
             if (lds < (size_t)16 * (512 + 4) * sizeof(float)) lds = (size_t)16 * (512 + 4) * sizeof(float);     // the epilogue tile
-            if (lds > 72 * 1024) continue;                          // two workgroups per CU
+            if (lds > VL_LDS_MAX) continue;
             if ((size_t)CC * G * 4 * (nbw * 16 / 4) > 1024) continue;   // weight slab: two float4 per thread
             const int ntz = (so + tz - 1) / tz, nty = (so + ty - 1) / ty;
             const double eff = (double)so * so * so / ((double)ntz * nty * 512.0);
@@ -491,27 +480,17 @@ extern "C" int rf_conv3d_valid_leaky_lds(const float* x, int n, int cin, int s, 
     RF_REQUIRE(convv_lds_plan(n, cin, s, cout, k, stride, a, variant, lds), RF_E_UNSUPPORTED,
                "rf_conv3d_valid_leaky_lds: shape not taken by the LDS-staged form (ask rf_conv3d_valid_lds_supported; use rf_conv3d_valid_leaky_mfma)");
     a.x = x; a.wp = w_packed; a.bias = bias; a.out = out; a.slope = slope;
-    const unsigned grid = (unsigned)a.ntz * a.nty * a.gz * n;
+    const dim3 grid((unsigned)a.ntz * a.nty * a.gz * n), block(512);
     hipStream_t st = (hipStream_t)stream;
-#define RF_VL_LAUNCH(NB_, CC_)                                                                                                   \
-    do {                                                                                                                         \
-        if (lds > 65536) {                                                                                                       \
-            static RfLdsOptIn opt_in;                                                                                            \
-            if (int rc = opt_in.ensure(reinterpret_cast<const void*>(k_convv_lds<NB_, CC_>), (int)lds, "rf_conv3d_valid_leaky_lds")) return rc; \
-        }                                                                                                                        \
-        hipLaunchKernelGGL((k_convv_lds<NB_, CC_>), dim3(grid), dim3(512), lds, st, a);                                          \
-    } while (0)
-    switch (variant) {
-        case 11: RF_VL_LAUNCH(1, 1); break;
-        case 12: RF_VL_LAUNCH(2, 1); break;
-        case 13: RF_VL_LAUNCH(3, 1); break;
-        case 21: RF_VL_LAUNCH(1, 2); break;
-        case 22: RF_VL_LAUNCH(2, 2); break;
-        default: RF_VL_LAUNCH(3, 2); break;
+    const char* who = "rf_conv3d_valid_leaky_lds";
+    switch (variant) {                                               // CC * 10 + NB
+        case 11: return rf_launch<k_convv_lds<1, 1>>(who, grid, block, lds, VL_LDS_MAX, st, a);
+        case 12: return rf_launch<k_convv_lds<2, 1>>(who, grid, block, lds, VL_LDS_MAX, st, a);
+        case 13: return rf_launch<k_convv_lds<3, 1>>(who, grid, block, lds, VL_LDS_MAX, st, a);
+        case 21: return rf_launch<k_convv_lds<1, 2>>(who, grid, block, lds, VL_LDS_MAX, st, a);
+        case 22: return rf_launch<k_convv_lds<2, 2>>(who, grid, block, lds, VL_LDS_MAX, st, a);
+        default: return rf_launch<k_convv_lds<3, 2>>(who, grid, block, lds, VL_LDS_MAX, st, a);
     }
-#undef RF_VL_LAUNCH
-    RF_CHECK_LAUNCH("rf_conv3d_valid_leaky_lds");
-    return RF_OK;
 }
 
 // ====================================================================================================================
@@ -811,6 +790,18 @@ extern "C" int rf_conv3d_valid_valu_supported(int n, int cin, int s, int cout, i
     return n > 0 && convv_valu_takes(cin, s, cout, k, stride) ? 1 : 0;
 }
 
+template <int COUT, int K>
+static int launch_valu_xt(const ConvVVArgs& a, dim3 grid, hipStream_t stream) {
+    return rf_launch<k_convv_valu_xt<COUT, K>>("rf_conv3d_valid_leaky_valu", grid, dim3(256), stream, a);
+}
+
+// `grid` tiles x cout / COUT blocks; the tile (`lds` bytes) fits the 64 KB a kernel gets without asking: the entry point refuses what does not
+constexpr size_t VV_LDS_MAX = 64 * 1024;
+template <int COUT, int K, int CC, int S = 0>
+static int launch_valu(const ConvVVArgs& a, unsigned grid, size_t lds, hipStream_t stream) {
+    return rf_launch<k_convv_valu<COUT, K, CC, S>>("rf_conv3d_valid_leaky_valu", dim3(grid, a.cout / COUT), dim3(256), lds, VV_LDS_MAX, stream, a);
+}
+
 // x [n][cin][s^3], w_t [cin][k^3][cout] (the OIDHW weight permuted to (1,2,3,4,0)), out [n][cout][so^3]
 extern "C" int rf_conv3d_valid_leaky_valu_ex(const float* x, int n, int cin, int s, const float* w_t, const float* bias, int cout, int k,
                                              int stride, float slope, void* out, int out_split, void* stream);
@@ -834,17 +825,14 @@ extern "C" int rf_conv3d_valid_leaky_valu_ex(const float* x, int n, int cin, int
         const size_t tiles = (size_t)((a.so + 3) / 4) * ((a.so + 3) / 4) * ((a.so + 63) / 64) * n;
         RF_REQUIRE(tiles < (1ull << 31), RF_E_INVALID, "rf_conv3d_valid_leaky_valu: too many tiles (%zu)", tiles);
         a.ty = 4; a.nty = (a.so + 3) / 4; a.ntz = (a.so + 3) / 4;
+        const dim3 grid((unsigned)tiles);
         hipStream_t sx = (hipStream_t)stream;
-#define RF_VX(COUT_, K_) hipLaunchKernelGGL((k_convv_valu_xt<COUT_, K_>), dim3((unsigned)tiles), dim3(256), 0, sx, a)
-        if (k == 5 && cout == 8) RF_VX(8, 5);
-        else if (k == 5 && cout == 12) RF_VX(12, 5);
-        else if (k == 5) RF_VX(16, 5);
-        else if (cout == 8) RF_VX(8, 3);
-        else if (cout == 12) RF_VX(12, 3);
-        else RF_VX(16, 3);
-#undef RF_VX
-        RF_CHECK_LAUNCH("rf_conv3d_valid_leaky_valu");
-        return RF_OK;
+        if (k == 5 && cout == 8) return launch_valu_xt<8, 5>(a, grid, sx);
+        if (k == 5 && cout == 12) return launch_valu_xt<12, 5>(a, grid, sx);
+        if (k == 5) return launch_valu_xt<16, 5>(a, grid, sx);
+        if (cout == 8) return launch_valu_xt<8, 3>(a, grid, sx);
+        if (cout == 12) return launch_valu_xt<12, 3>(a, grid, sx);
+        return launch_valu_xt<16, 3>(a, grid, sx);
     }
     a.ty = 256 / a.so;
     if (a.ty > a.so) a.ty = a.so;
@@ -852,25 +840,19 @@ extern "C" int rf_conv3d_valid_leaky_valu_ex(const float* x, int n, int cin, int
     a.ntz = (a.so + 3) / 4;
     const int cc = cin >= 4 ? 4 : 1;
     const size_t lds = ((size_t)cc * (4 + k - 1) * (a.ty + k - 1) * s) * sizeof(float);
-    RF_REQUIRE(lds <= 64 * 1024, RF_E_UNSUPPORTED, "rf_conv3d_valid_leaky_valu: tile of %zu bytes does not fit LDS", lds);
+    RF_REQUIRE(lds <= VV_LDS_MAX, RF_E_UNSUPPORTED, "rf_conv3d_valid_leaky_valu: tile of %zu bytes does not fit LDS", lds);
     const unsigned grid = (unsigned)a.ntz * a.nty * n;
     hipStream_t st = (hipStream_t)stream;
-#define RF_VV(COUT_, K_, CC_) hipLaunchKernelGGL((k_convv_valu<COUT_, K_, CC_>), dim3(grid, cout / COUT_), dim3(256), lds, st, a)
-#define RF_VVS(COUT_, K_, CC_, S_) hipLaunchKernelGGL((k_convv_valu<COUT_, K_, CC_, S_>), dim3(grid, cout / COUT_), dim3(256), lds, st, a)
     // the shipped encoders' layers with their input edge as a constant (PCPatch48: 48; Patch32: 32 -> 28; model/retrieval.py:4-28,217-243).
     // Not the 12 -> 24 @44 layer: specialised it allocates 234 instead of 196 VGPRs and runs 13.4 -> 22.4 ms.
-    if (k == 5 && cout == 12 && s == 48) RF_VVS(12, 5, 1, 48);
-    else if (k == 5 && cout == 8 && s == 32) RF_VVS(8, 5, 1, 32);
-    else if (k == 3 && cin == 8 && cout == 16 && s == 28) RF_VVS(16, 3, 4, 28);
-    else if (k == 5 && cout == 8) RF_VV(8, 5, 1);
-    else if (k == 5) RF_VV(12, 5, 1);
-    else if (cin == 1 && cout == 8) RF_VV(8, 3, 1);
-    else if (cin == 1 && cout == 12) RF_VV(12, 3, 1);
-    else if (cin == 1) RF_VV(16, 3, 1);
-    else if (cout == 16) RF_VV(16, 3, 4);
-    else RF_VV(24, 3, 4);
-#undef RF_VV
-#undef RF_VVS
-    RF_CHECK_LAUNCH("rf_conv3d_valid_leaky_valu");
-    return RF_OK;
+    if (k == 5 && cout == 12 && s == 48) return launch_valu<12, 5, 1, 48>(a, grid, lds, st);
+    if (k == 5 && cout == 8 && s == 32) return launch_valu<8, 5, 1, 32>(a, grid, lds, st);
+    if (k == 3 && cin == 8 && cout == 16 && s == 28) return launch_valu<16, 3, 4, 28>(a, grid, lds, st);
+    if (k == 5 && cout == 8) return launch_valu<8, 5, 1>(a, grid, lds, st);
+    if (k == 5) return launch_valu<12, 5, 1>(a, grid, lds, st);
+    if (cin == 1 && cout == 8) return launch_valu<8, 3, 1>(a, grid, lds, st);
+    if (cin == 1 && cout == 12) return launch_valu<12, 3, 1>(a, grid, lds, st);
+    if (cin == 1) return launch_valu<16, 3, 1>(a, grid, lds, st);
+    if (cout == 16) return launch_valu<16, 3, 4>(a, grid, lds, st);
+    return launch_valu<24, 3, 4>(a, grid, lds, st);
 }

@@ -162,13 +162,11 @@ extern "C" int rf_convv_split_pack_weight(const float* w_oidhw, int cout, int ci
     RF_REQUIRE(convv_split_plan(cin, s, cout, k, stride, a, nb, lds), RF_E_UNSUPPORTED,
                "rf_convv_split_pack_weight: layer not taken by the split form (ask rf_conv3d_valid_split_supported)");
     const size_t total = (rf_convv_split_packed_bytes(cout, cin, k, s, stride) - (size_t)a.hdr * 4) / 16;
-    hipLaunchKernelGGL(k_convv_split_header, dim3((unsigned)((a.hdr + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a, reinterpret_cast<int*>(w_packed));
+    const char* who = "rf_convv_split_pack_weight";
+    if (int rc = rf_launch<k_convv_split_header>(who, dim3((unsigned)((a.hdr + 255) / 256)), dim3(256), (hipStream_t)stream, a, reinterpret_cast<int*>(w_packed))) return rc;
     const size_t nreal = (size_t)a.nchunk * a.ksteps * a.nbt * 128;
-    const size_t want = (total + 255) / 256;
-    hipLaunchKernelGGL(k_convv_split_pack, dim3((unsigned)(want < 4096 ? want : 4096)), dim3(256), 0, (hipStream_t)stream, w_oidhw, cout, cin,
-                       k * k * k, a.cgc, a.ksteps, a.nbt, nreal, reinterpret_cast<h8*>(w_packed) + a.hdr / 4, total);
-    RF_CHECK_LAUNCH("rf_convv_split_pack_weight");
-    return RF_OK;
+    return rf_launch<k_convv_split_pack>(who, dim3(rf_blocks(total, 256, 4096)), dim3(256), (hipStream_t)stream, w_oidhw, cout, cin, k * k * k, a.cgc, a.ksteps, a.nbt,
+                                         nreal, reinterpret_cast<h8*>(w_packed) + a.hdr / 4, total);
 }
 
 // ------------------------------------------------------------------------------------------------------------------- kernel
@@ -194,8 +192,7 @@ __global__ __launch_bounds__(VS_NT, WPE) void k_convv_split(ConvVSArgs a) {
     const size_t ivol = (size_t)s * s * s;
 
     // XCD-aware 1-D grid as in k_convv_lds: an XCD walks whole windows (tiles fastest, then cout block groups)
-    const unsigned total = gridDim.x, per = total >> 3, rem = total & 7u, xk = blockIdx.x & 7u;
-    const unsigned lb = xk * per + (xk < rem ? xk : rem) + (blockIdx.x >> 3);
+    const unsigned lb = rf_xcd_contiguous(blockIdx.x, gridDim.x);
     const unsigned tiles = (unsigned)(a.ntz * a.nty * a.ntx);
     const unsigned tb = lb % tiles, zb = (lb / tiles) % (unsigned)a.gz;
     const int nn = (int)(lb / (tiles * (unsigned)a.gz));
@@ -434,32 +431,21 @@ extern "C" int rf_conv3d_valid_leaky_split_ex(const void* x, int in_split, int n
     a.out_pre = out_split ? 1 : 0;
     const size_t grid64 = (size_t)a.ntz * a.nty * a.ntx * a.gz * n;
     RF_REQUIRE(grid64 < (1ull << 31), RF_E_INVALID, "rf_conv3d_valid_leaky_split: too many tiles (%zu)", grid64);
-    const unsigned grid = (unsigned)grid64;
+    const dim3 grid((unsigned)grid64), block(VS_NT);
     hipStream_t st = (hipStream_t)stream;
-#define RF_VS_LAUNCH(NB_, WPE_, PRE_)                                                                                            \
-    do {                                                                                                                         \
-        if (lds > 65536) {                                                                                                       \
-            static RfLdsOptIn opt_in;                                                                                            \
-            if (int rc = opt_in.ensure(reinterpret_cast<const void*>(k_convv_split<NB_, WPE_, PRE_>), (int)VS_LDS_MAX, "rf_conv3d_valid_leaky_split")) return rc; \
-        }                                                                                                                        \
-        hipLaunchKernelGGL((k_convv_split<NB_, WPE_, PRE_>), dim3(grid), dim3(VS_NT), lds, st, a);                               \
-    } while (0)
+    const char* who = "rf_conv3d_valid_leaky_split";
     if (in_split) {
         switch (nbw) {
-            case 1: RF_VS_LAUNCH(1, 3, true); break;
-            case 2: RF_VS_LAUNCH(2, 3, true); break;
-            default: RF_VS_LAUNCH(3, 2, true); break;
-        }
-    } else {
-        switch (nbw) {
-            case 1: RF_VS_LAUNCH(1, 3, false); break;
-            case 2: RF_VS_LAUNCH(2, 3, false); break;
-            default: RF_VS_LAUNCH(3, 2, false); break;
+            case 1: return rf_launch<k_convv_split<1, 3, true>>(who, grid, block, lds, VS_LDS_MAX, st, a);
+            case 2: return rf_launch<k_convv_split<2, 3, true>>(who, grid, block, lds, VS_LDS_MAX, st, a);
+            default: return rf_launch<k_convv_split<3, 2, true>>(who, grid, block, lds, VS_LDS_MAX, st, a);
         }
     }
-#undef RF_VS_LAUNCH
-    RF_CHECK_LAUNCH("rf_conv3d_valid_leaky_split");
-    return RF_OK;
+    switch (nbw) {
+        case 1: return rf_launch<k_convv_split<1, 3, false>>(who, grid, block, lds, VS_LDS_MAX, st, a);
+        case 2: return rf_launch<k_convv_split<2, 3, false>>(who, grid, block, lds, VS_LDS_MAX, st, a);
+        default: return rf_launch<k_convv_split<3, 2, false>>(who, grid, block, lds, VS_LDS_MAX, st, a);
+    }
 }
 
 extern "C" int rf_conv3d_valid_leaky_split(const float* x, int n, int cin, int s, const void* w_packed, const float* bias, int cout, int k,

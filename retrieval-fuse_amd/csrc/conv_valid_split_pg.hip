@@ -131,11 +131,10 @@ extern "C" int rf_convv_split_pg_pack_weight(const float* w_oidhw, int cout, int
     RF_REQUIRE(convv_pg_plan(cin, s, cout, k, stride, a), RF_E_UNSUPPORTED,
                "rf_convv_split_pg_pack_weight: layer not taken by the persistent grid form (ask rf_conv3d_valid_split_pg_supported)");
     const size_t total = (size_t)a.ksteps * 2 * 64;
-    hipLaunchKernelGGL(k_convv_pg_header, dim3((unsigned)((a.hdr + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a, reinterpret_cast<int*>(w_packed));
-    hipLaunchKernelGGL(k_convv_pg_pack, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a, w_oidhw,
-                       reinterpret_cast<h8*>(w_packed) + a.hdr / 4, total);
-    RF_CHECK_LAUNCH("rf_convv_split_pg_pack_weight");
-    return RF_OK;
+    const char* who = "rf_convv_split_pg_pack_weight";
+    if (int rc = rf_launch<k_convv_pg_header>(who, dim3((unsigned)((a.hdr + 255) / 256)), dim3(256), (hipStream_t)stream, a, reinterpret_cast<int*>(w_packed))) return rc;
+    return rf_launch<k_convv_pg_pack>(who, dim3((unsigned)((total + 255) / 256)), dim3(256), (hipStream_t)stream, a, w_oidhw, reinterpret_cast<h8*>(w_packed) + a.hdr / 4,
+                                      total);
 }
 
 // ------------------------------------------------------------------------------------------------------------------- kernel
@@ -448,11 +447,7 @@ extern "C" int rf_conv3d_valid_leaky_split_pg(const void* x, int n, int cin, int
     if (grid < 8) grid = 8;
     while ((size_t)grid * 2 > tiles64 && grid > 8) grid -= 8;
     const size_t lds = convv_pg_lds_bytes(a);
-    static RfLdsOptIn opt_in;
     RF_REQUIRE(a.ksteps == 21 && a.rs == 144 && a.ps == 896 && a.plane == 16640 && a.cout > 16 && a.cout <= 24, RF_E_UNSUPPORTED,
                "rf_conv3d_valid_leaky_split_pg: plan differs from the instantiation built");
-    if (int rc = opt_in.ensure(reinterpret_cast<const void*>(k_convv_split_pg<21, 3, 144, 896, 16640>), (int)PG_LDS_MAX, "rf_conv3d_valid_leaky_split_pg")) return rc;
-    hipLaunchKernelGGL((k_convv_split_pg<21, 3, 144, 896, 16640>), dim3(grid), dim3(PG_NT), lds, (hipStream_t)stream, a);
-    RF_CHECK_LAUNCH("rf_conv3d_valid_leaky_split_pg");
-    return RF_OK;
+    return rf_launch<k_convv_split_pg<21, 3, 144, 896, 16640>>("rf_conv3d_valid_leaky_split_pg", dim3(grid), dim3(PG_NT), lds, PG_LDS_MAX, (hipStream_t)stream, a);
 }

@@ -22,11 +22,8 @@ extern "C" size_t rf_linear_packed_floats(int nout, int nin) { return (size_t)rf
 extern "C" int rf_linear_pack_weight(const float* w, int nout, int nin, float* wp, void* stream) {
     RF_REQUIRE(w && wp && nout > 0 && nin > 0, RF_E_INVALID, "rf_linear_pack_weight: bad arguments");
     const size_t total = rf_linear_packed_floats(nout, nin);
-    const size_t want = (total + 255) / 256;
-    hipLaunchKernelGGL(k_linear_pack, dim3((unsigned)(want < 1024 ? want : 1024)), dim3(256), 0, (hipStream_t)stream, w, nout, nin,
-                       rf_round_up(nin, 4), rf_round_up(nout, 16), wp);
-    RF_CHECK_LAUNCH("rf_linear_pack_weight");
-    return RF_OK;
+    return rf_launch<k_linear_pack>("rf_linear_pack_weight", dim3(rf_blocks(total, 256, 1024)), dim3(256), (hipStream_t)stream, w, nout, nin,
+                                    rf_round_up(nin, 4), rf_round_up(nout, 16), wp);
 }
 
 template <int NB>
@@ -123,15 +120,11 @@ extern "C" int rf_linear(const float* x, int rows, int nin, const float* w_packe
     const int nin4 = rf_round_up(nin, 4), nout16 = rf_round_up(nout, 16);
     hipStream_t s = (hipStream_t)stream;
     const unsigned gx = (unsigned)((rows + 127) / 128);
-    if (nout16 <= 32) {
-        hipLaunchKernelGGL(k_linear_mfma<2>, dim3(gx, (nout16 + 31) / 32), dim3(256), 0, s, x, rows, nin, w_packed, nin4, nout16, bias, nout, act,
-                           slope, y);
-    } else {
-        hipLaunchKernelGGL(k_linear_mfma<4>, dim3(gx, (nout16 + 63) / 64), dim3(256), 0, s, x, rows, nin, w_packed, nin4, nout16, bias, nout, act,
-                           slope, y);
-    }
-    RF_CHECK_LAUNCH("rf_linear");
-    return RF_OK;
+    if (nout16 <= 32)
+        return rf_launch<k_linear_mfma<2>>("rf_linear", dim3(gx, (nout16 + 31) / 32), dim3(256), s, x, rows, nin, w_packed, nin4, nout16, bias, nout, act,
+                                           slope, y);
+    return rf_launch<k_linear_mfma<4>>("rf_linear", dim3(gx, (nout16 + 63) / 64), dim3(256), s, x, rows, nin, w_packed, nin4, nout16, bias, nout, act,
+                                       slope, y);
 }
 
 // ---------------------------------------------------------------------------------------------------- weight gradient
@@ -140,7 +133,7 @@ extern "C" int rf_linear(const float* x, int rows, int nin, const float* w_packe
 // K is the row count of the batch (10^4..10^6), M and N are layer widths (<= 512): a split-K GEMM.  Both operands are already in
 // MFMA operand order -- lane l of an A read takes a[k0 + l/16][m0 + l%16], of a B read b[k0 + l/16][n0 + l%16], i.e. 16 consecutive
 // floats of 4 consecutive rows -- so they go global -> VGPR -> MFMA directly, no LDS.  A workgroup owns a 32 x 64 tile of dW and one
-// K slice; its 4 waves interleave the slice's k-steps, reduce through LDS, and write an fp32 partial; k_linear_wgrad_reduce sums the
+// K slice; its 4 waves interleave the slice's k-steps, reduce through LDS, and write an fp32 partial; rf_slice_sum (common.h) sums the
 // slices in float64 in a fixed order (deterministic, no atomics).
 __global__ __launch_bounds__(256) void k_linear_wgrad(const float* __restrict__ a, const float* __restrict__ b, int K, int M, int N, int kslice,
                                                      float* __restrict__ partial) {
@@ -206,14 +199,6 @@ __global__ __launch_bounds__(256) void k_linear_wgrad(const float* __restrict__ 
     }
 }
 
-__global__ void k_linear_wgrad_reduce(const float* __restrict__ partial, int slices, size_t mn, float* __restrict__ out) {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < mn; i += (size_t)gridDim.x * blockDim.x) {
-        double s = 0.0;
-        for (int z = 0; z < slices; ++z) s += (double)partial[(size_t)z * mn + i];
-        out[i] = (float)s;
-    }
-}
-
 static void linear_wgrad_plan(int K, int M, int N, int& slices, int& kslice) {
     const int tiles = ((M + 31) / 32) * ((N + 63) / 64);
     int want = (1024 + tiles - 1) / tiles;                           // ~4 workgroups per CU
@@ -236,12 +221,9 @@ extern "C" int rf_linear_wgrad(const float* a, const float* b, int K, int M, int
     int slices, kslice;
     linear_wgrad_plan(K, M, N, slices, kslice);
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_linear_wgrad, dim3((M + 31) / 32, (N + 63) / 64, slices), dim3(256), 0, s, a, b, K, M, N, kslice, static_cast<float*>(ws));
-    RF_CHECK_LAUNCH("rf_linear_wgrad");
-    const size_t mn = (size_t)M * N;
-    hipLaunchKernelGGL(k_linear_wgrad_reduce, dim3((unsigned)((mn + 255) / 256)), dim3(256), 0, s, static_cast<const float*>(ws), slices, mn, dw);
-    RF_CHECK_LAUNCH("rf_linear_wgrad(reduce)");
-    return RF_OK;
+    if (int rc = rf_launch<k_linear_wgrad>("rf_linear_wgrad", dim3((M + 31) / 32, (N + 63) / 64, slices), dim3(256), s, a, b, K, M, N, kslice, static_cast<float*>(ws)))
+        return rc;
+    return rf_slice_sum(static_cast<const float*>(ws), slices, (size_t)M * N, dw, s, "rf_linear_wgrad(reduce)");
 }
 
 // one wave per row
@@ -259,8 +241,5 @@ __global__ __launch_bounds__(256) void k_l2norm_rows(float* __restrict__ x, int 
 
 extern "C" int rf_l2_normalize_rows(float* x, int rows, int dim, float eps, void* stream) {
     RF_REQUIRE(x && rows > 0 && dim > 0, RF_E_INVALID, "rf_l2_normalize_rows: bad arguments");
-    const int want = (rows + 3) / 4;
-    hipLaunchKernelGGL(k_l2norm_rows, dim3(want < 2048 ? want : 2048), dim3(256), 0, (hipStream_t)stream, x, rows, dim, eps);
-    RF_CHECK_LAUNCH("rf_l2_normalize_rows");
-    return RF_OK;
+    return rf_launch<k_l2norm_rows>("rf_l2_normalize_rows", dim3(rf_blocks(rows, 4, 2048)), dim3(256), (hipStream_t)stream, x, rows, dim, eps);
 }

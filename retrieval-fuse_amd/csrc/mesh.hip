@@ -83,20 +83,15 @@ __global__ __launch_bounds__(256) void k_mc_emit(const float* __restrict__ sdf, 
 extern "C" int rf_mc_classify(const float* sdf, int x, int y, int z, float level, const signed char* tri_count, int* cube_ntri, int* edge_flag, void* stream) {
     RF_REQUIRE(sdf && tri_count && cube_ntri && edge_flag && x >= 2 && y >= 2 && z >= 2 && (size_t)x * y * z * 3 < (1ull << 31), RF_E_INVALID,
                "rf_mc_classify: needs a volume of at least 2^3 and fewer than 2^31 / 3 voxels (got %d x %d x %d)", x, y, z);
-    const size_t want = ((size_t)x * y * z + 255) / 256;
-    hipLaunchKernelGGL(k_mc_classify, dim3((unsigned)(want < 65536 ? want : 65536)), dim3(256), 0, (hipStream_t)stream, sdf, x, y, z, level, tri_count, cube_ntri, edge_flag);
-    RF_CHECK_LAUNCH("rf_mc_classify");
-    return RF_OK;
+    return rf_launch<k_mc_classify>("rf_mc_classify", dim3(rf_blocks((size_t)x * y * z, 256, 65536)), dim3(256), (hipStream_t)stream, sdf, x, y, z, level, tri_count,
+                                    cube_ntri, edge_flag);
 }
 
 extern "C" int rf_mc_emit(const float* sdf, int x, int y, int z, float level, const signed char* tri_table, const long long* cube_off, const long long* edge_off,
                           const int* cube_ntri, const int* edge_flag, float* verts, int* tris, void* stream) {
     RF_REQUIRE(sdf && tri_table && cube_off && edge_off && cube_ntri && edge_flag && verts && tris && x >= 2 && y >= 2 && z >= 2, RF_E_INVALID, "rf_mc_emit: bad arguments");
-    const size_t want = ((size_t)x * y * z + 255) / 256;
-    hipLaunchKernelGGL(k_mc_emit, dim3((unsigned)(want < 65536 ? want : 65536)), dim3(256), 0, (hipStream_t)stream, sdf, x, y, z, level, tri_table, cube_off, edge_off,
-                       cube_ntri, edge_flag, verts, tris);
-    RF_CHECK_LAUNCH("rf_mc_emit");
-    return RF_OK;
+    return rf_launch<k_mc_emit>("rf_mc_emit", dim3(rf_blocks((size_t)x * y * z, 256, 65536)), dim3(256), (hipStream_t)stream, sdf, x, y, z, level, tri_table, cube_off,
+                                edge_off, cube_ntri, edge_flag, verts, tris);
 }
 
 
@@ -125,7 +120,5 @@ extern "C" int rf_paste_chunks(const float* df, int b, const int* sel, const lon
     RF_REQUIRE(df && sel && dst && flat && b > 0 && m >= 0, RF_E_INVALID, "rf_paste_chunks: bad arguments");
     RF_REQUIRE(sy >= 64 && sx >= 64 * sy && sy % 2 == 0 && sx % 2 == 0, RF_E_INVALID, "rf_paste_chunks: canvas strides sx=%lld sy=%lld (need even, sy >= 64, sx >= 64 sy)", sx, sy);
     if (m == 0) return RF_OK;
-    hipLaunchKernelGGL(k_paste_chunks, dim3((unsigned)m * 64u), dim3(256), 0, (hipStream_t)stream, df, sel, dst, sx, sy, round_half, flat);
-    RF_CHECK_LAUNCH("rf_paste_chunks");
-    return RF_OK;
+    return rf_launch<k_paste_chunks>("rf_paste_chunks", dim3((unsigned)m * 64u), dim3(256), (hipStream_t)stream, df, sel, dst, sx, sy, round_half, flat);
 }

@@ -310,19 +310,15 @@ __global__ __launch_bounds__(256) void k_voxelize(const float* __restrict__ vert
 extern "C" int rf_eval_face_areas(const float* vertices, int n_vert, const int* triangles, int n_tri, double* areas, void* stream) {
     RF_REQUIRE(vertices && triangles && areas && n_vert >= 1 && n_tri >= 1, RF_E_INVALID, "rf_eval_face_areas: bad arguments");
     RF_REQUIRE(n_vert <= (1 << 28) && n_tri <= (1 << 28), RF_E_UNSUPPORTED, "rf_eval_face_areas: %d vertices, %d triangles (at most 2^28 each)", n_vert, n_tri);
-    hipLaunchKernelGGL(k_face_areas, dim3((n_tri + 255) / 256), dim3(256), 0, (hipStream_t)stream, vertices, n_vert, triangles, n_tri, areas);
-    RF_CHECK_LAUNCH("rf_eval_face_areas");
-    return RF_OK;
+    return rf_launch<k_face_areas>("rf_eval_face_areas", dim3((n_tri + 255) / 256), dim3(256), (hipStream_t)stream, vertices, n_vert, triangles, n_tri, areas);
 }
 
 extern "C" int rf_eval_sample_surface(const float* vertices, const int* triangles, const double* cdf, int n_tri, int n, int64_t seed, float* points,
                                       int* face, float* normals, void* stream) {
     RF_REQUIRE(vertices && triangles && cdf && points && face && normals && n_tri >= 1 && n >= 1, RF_E_INVALID, "rf_eval_sample_surface: bad arguments");
     RF_REQUIRE(n_tri <= (1 << 28) && n <= (1 << 28), RF_E_UNSUPPORTED, "rf_eval_sample_surface: %d triangles, %d samples (at most 2^28 each)", n_tri, n);
-    hipLaunchKernelGGL(k_sample_surface, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, vertices, triangles, cdf, n_tri, n,
-                       (unsigned long long)seed, points, face, normals);
-    RF_CHECK_LAUNCH("rf_eval_sample_surface");
-    return RF_OK;
+    return rf_launch<k_sample_surface>("rf_eval_sample_surface", dim3((n + 255) / 256), dim3(256), (hipStream_t)stream, vertices, triangles, cdf, n_tri, n,
+                                       (unsigned long long)seed, points, face, normals);
 }
 
 extern "C" size_t rf_eval_nearest3_ws_bytes(int n_src, int n_tgt) {
@@ -344,16 +340,9 @@ extern "C" int rf_eval_nearest3(const float* src, int n_src, const float* tgt, i
     double* part_d2 = reinterpret_cast<double*>(ws);
     int* part_idx = reinterpret_cast<int*>(reinterpret_cast<char*>(ws) + align256((size_t)splits * n_src * sizeof(double)));
     hipStream_t s = (hipStream_t)stream;
-    if (used == 1) {
-        hipLaunchKernelGGL(k_nn_scan, dim3(src_blocks, 1), dim3(kNnThreads), 0, s, src, n_src, tgt, n_tgt, chunk, d2, idx);
-        RF_CHECK_LAUNCH("rf_eval_nearest3 (scan)");
-        return RF_OK;
-    }
-    hipLaunchKernelGGL(k_nn_scan, dim3(src_blocks, used), dim3(kNnThreads), 0, s, src, n_src, tgt, n_tgt, chunk, part_d2, part_idx);
-    RF_CHECK_LAUNCH("rf_eval_nearest3 (scan)");
-    hipLaunchKernelGGL(k_nn_reduce, dim3((n_src + 255) / 256), dim3(256), 0, s, part_d2, part_idx, n_src, used, d2, idx);
-    RF_CHECK_LAUNCH("rf_eval_nearest3 (reduce)");
-    return RF_OK;
+    if (used == 1) return rf_launch<k_nn_scan>("rf_eval_nearest3 (scan)", dim3(src_blocks, 1), dim3(kNnThreads), s, src, n_src, tgt, n_tgt, chunk, d2, idx);
+    if (int rc = rf_launch<k_nn_scan>("rf_eval_nearest3 (scan)", dim3(src_blocks, used), dim3(kNnThreads), s, src, n_src, tgt, n_tgt, chunk, part_d2, part_idx)) return rc;
+    return rf_launch<k_nn_reduce>("rf_eval_nearest3 (reduce)", dim3((n_src + 255) / 256), dim3(256), s, part_d2, part_idx, n_src, used, d2, idx);
 }
 
 extern "C" size_t rf_eval_p2p_stats_ws_bytes(int n) { return n < 1 ? 0 : align256((size_t)kStatBlocks * 3 * sizeof(double)); }
@@ -371,14 +360,12 @@ extern "C" int rf_eval_p2p_stats(const double* d2, const int* idx, const float* 
         rf_set_error("rf_eval_p2p_stats: cannot clear the counts");
         return RF_E_LAUNCH;
     }
-    const int blocks = (int)(((long long)n + 255) / 256 < kStatBlocks ? ((long long)n + 255) / 256 : kStatBlocks);
+    const int blocks = (int)rf_blocks(n, 256, kStatBlocks);
     unsigned long long* cnt = reinterpret_cast<unsigned long long*>(counts);
-    hipLaunchKernelGGL(k_p2p_stats, dim3(blocks), dim3(256), 0, s, d2, idx, normals_src, normals_tgt, n, n_tgt, thresholds, n_thr, dist, dots, cnt,
-                       reinterpret_cast<double*>(ws));
-    RF_CHECK_LAUNCH("rf_eval_p2p_stats");
-    hipLaunchKernelGGL(k_p2p_finish, dim3(1), dim3(256), 0, s, reinterpret_cast<const double*>(ws), blocks, cnt, n_thr, sums);
-    RF_CHECK_LAUNCH("rf_eval_p2p_stats (finish)");
-    return RF_OK;
+    if (int rc = rf_launch<k_p2p_stats>("rf_eval_p2p_stats", dim3(blocks), dim3(256), s, d2, idx, normals_src, normals_tgt, n, n_tgt, thresholds, n_thr, dist, dots, cnt,
+                                        reinterpret_cast<double*>(ws)))
+        return rc;
+    return rf_launch<k_p2p_finish>("rf_eval_p2p_stats (finish)", dim3(1), dim3(256), s, reinterpret_cast<const double*>(ws), blocks, cnt, n_thr, sums);
 }
 
 extern "C" int rf_eval_voxelize(const float* vertices, int n_vert, const int* triangles, int n_tri, float pitch, int lo_x, int lo_y, int lo_z, int dim_x,
@@ -391,8 +378,6 @@ extern "C" int rf_eval_voxelize(const float* vertices, int n_vert, const int* tr
     RF_REQUIRE(lo_x > -far && lo_y > -far && lo_z > -far && lo_x < far && lo_y < far && lo_z < far, RF_E_UNSUPPORTED,
                "rf_eval_voxelize: grid origin (%d, %d, %d) outside +-2^30", lo_x, lo_y, lo_z);
     RF_REQUIRE(n_tri <= (1 << 28) && n_vert <= (1 << 28), RF_E_UNSUPPORTED, "rf_eval_voxelize: %d vertices, %d triangles (at most 2^28 each)", n_vert, n_tri);
-    hipLaunchKernelGGL(k_voxelize, dim3((n_tri + 3) / 4), dim3(256), 0, (hipStream_t)stream, vertices, n_vert, triangles, n_tri, pitch, lo_x, lo_y, lo_z,
-                       dim_x, dim_y, dim_z, grid);
-    RF_CHECK_LAUNCH("rf_eval_voxelize");
-    return RF_OK;
+    return rf_launch<k_voxelize>("rf_eval_voxelize", dim3((n_tri + 3) / 4), dim3(256), (hipStream_t)stream, vertices, n_vert, triangles, n_tri, pitch, lo_x, lo_y, lo_z,
+                                 dim_x, dim_y, dim_z, grid);
 }

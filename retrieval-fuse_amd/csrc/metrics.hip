@@ -222,13 +222,10 @@ extern "C" int rf_occupancy_stats(const void* pred, int pred_kind, float pred_th
         rf_set_error("rf_occupancy_stats: cannot clear the output");
         return RF_E_LAUNCH;
     }
-    hipLaunchKernelGGL(k_occ_pack, dim3((unsigned)grid_pack), dim3(256), 0, s, pred, pred_kind, pred_thr, target, target_kind, target_thr, d, h, w,
-                       bits_p, bits_t, o);
-    RF_CHECK_LAUNCH("rf_occupancy_stats (pack)");
+    if (int rc = rf_launch<k_occ_pack>("rf_occupancy_stats (pack)", dim3((unsigned)grid_pack), dim3(256), s, pred, pred_kind, pred_thr, target, target_kind, target_thr,
+                                       d, h, w, bits_p, bits_t, o))
+        return rc;
     if (!chamfer) return RF_OK;
-    hipLaunchKernelGGL(k_minplus<true>, dim3((unsigned)grid_h), dim3(256), 0, s, b, d, h, w, bits_p, bits_t, g2, o);
-    RF_CHECK_LAUNCH("rf_occupancy_stats (min-plus along h)");
-    hipLaunchKernelGGL(k_minplus<false>, dim3((unsigned)grid_d), dim3(256), 0, s, b, d, h, w, bits_p, bits_t, g2, o);
-    RF_CHECK_LAUNCH("rf_occupancy_stats (min-plus along d)");
-    return RF_OK;
+    if (int rc = rf_launch<k_minplus<true>>("rf_occupancy_stats (min-plus along h)", dim3((unsigned)grid_h), dim3(256), s, b, d, h, w, bits_p, bits_t, g2, o)) return rc;
+    return rf_launch<k_minplus<false>>("rf_occupancy_stats (min-plus along d)", dim3((unsigned)grid_d), dim3(256), s, b, d, h, w, bits_p, bits_t, g2, o);
 }

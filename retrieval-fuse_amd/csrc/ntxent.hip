@@ -354,10 +354,8 @@ extern "C" int rf_ntx_plan(const uint8_t* occupancy, int n_rows, int num_slices,
     RF_REQUIRE(layout_of(n_rows, num_slices, max_rows, dim, &L), RF_E_UNSUPPORTED, kRange, "rf_ntx_plan", n_rows, num_slices, max_rows, dim);
     RF_REQUIRE(ws_bytes >= L.total, RF_E_WORKSPACE, "rf_ntx_plan: workspace of %zu bytes, needs %zu", ws_bytes, L.total);
     const Ws p = pointers(L, ws);
-    hipLaunchKernelGGL(k_ntx_plan, dim3(1), dim3(kPlanThreads), 0, (hipStream_t)stream, occupancy, n_rows, num_slices, max_rows, L.tiles_max, p.hdr, p.rows,
-                       p.tiles, p.sel, reinterpret_cast<long long*>(counts));
-    RF_CHECK_LAUNCH("rf_ntx_plan");
-    return RF_OK;
+    return rf_launch<k_ntx_plan>("rf_ntx_plan", dim3(1), dim3(kPlanThreads), (hipStream_t)stream, occupancy, n_rows, num_slices, max_rows, L.tiles_max, p.hdr, p.rows,
+                                 p.tiles, p.sel, reinterpret_cast<long long*>(counts));
 }
 
 extern "C" int rf_ntx_forward(const float* zis, const float* zjs, const float* iou, int n_rows, int num_slices, int max_rows, int dim, int cosine, float tau,
@@ -370,13 +368,12 @@ extern "C" int rf_ntx_forward(const float* zis, const float* zjs, const float* i
     const Ws p = pointers(L, ws);
     const Temp tp{tau, sig_scale, sig_shift};
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_ntx_rows, dim3((unsigned)((2 * (size_t)max_rows + 3) / 4)), dim3(kThreads), 0, s, zis, zjs, p.hdr, p.rows, max_rows, dim, cosine, p.w, p.nrm);
-    RF_CHECK_LAUNCH("rf_ntx_forward (rows)");
-    hipLaunchKernelGGL(k_ntx_lse, dim3((unsigned)L.tiles_max), dim3(kThreads), 0, s, iou, p.hdr, p.tiles, p.w, max_rows, dim, tp, p.lse, p.term);
-    RF_CHECK_LAUNCH("rf_ntx_forward");
-    hipLaunchKernelGGL(k_ntx_finish, dim3(1), dim3(kThreads), 0, s, p.hdr, p.term, max_rows, loss);
-    RF_CHECK_LAUNCH("rf_ntx_forward (finish)");
-    return RF_OK;
+    if (int rc = rf_launch<k_ntx_rows>("rf_ntx_forward (rows)", dim3((unsigned)((2 * (size_t)max_rows + 3) / 4)), dim3(kThreads), s, zis, zjs, p.hdr, p.rows, max_rows,
+                                       dim, cosine, p.w, p.nrm))
+        return rc;
+    if (int rc = rf_launch<k_ntx_lse>("rf_ntx_forward", dim3((unsigned)L.tiles_max), dim3(kThreads), s, iou, p.hdr, p.tiles, p.w, max_rows, dim, tp, p.lse, p.term))
+        return rc;
+    return rf_launch<k_ntx_finish>("rf_ntx_forward (finish)", dim3(1), dim3(kThreads), s, p.hdr, p.term, max_rows, loss);
 }
 
 extern "C" int rf_ntx_backward(const float* iou, const float* grad_loss, int n_rows, int num_slices, int max_rows, int dim, int cosine, float tau, float sig_scale,
@@ -388,10 +385,7 @@ extern "C" int rf_ntx_backward(const float* iou, const float* grad_loss, int n_r
     RF_REQUIRE(ws_bytes >= L.total, RF_E_WORKSPACE, "rf_ntx_backward: workspace of %zu bytes, needs %zu", ws_bytes, L.total);
     const Ws p = pointers(L, const_cast<void*>(ws));
     const Temp tp{tau, sig_scale, sig_shift};
-    const size_t elems = (size_t)n_rows * dim;
-    const unsigned zero_wgs = (unsigned)((elems + 4 * kThreads - 1) / (4 * kThreads) < 1024 ? (elems + 4 * kThreads - 1) / (4 * kThreads) : 1024);
-    hipLaunchKernelGGL(k_ntx_bwd, dim3((unsigned)L.tiles_max + zero_wgs), dim3(kThreads), 0, (hipStream_t)stream, iou, grad_loss, p.hdr, p.rows, p.tiles, p.sel, p.w,
-                       p.nrm, p.lse, n_rows, max_rows, dim, cosine, tp, L.tiles_max, dzis, dzjs);
-    RF_CHECK_LAUNCH("rf_ntx_backward");
-    return RF_OK;
+    const unsigned zero_wgs = rf_blocks((size_t)n_rows * dim, 4 * kThreads, 1024);
+    return rf_launch<k_ntx_bwd>("rf_ntx_backward", dim3((unsigned)L.tiles_max + zero_wgs), dim3(kThreads), (hipStream_t)stream, iou, grad_loss, p.hdr, p.rows, p.tiles,
+                                p.sel, p.w, p.nrm, p.lse, n_rows, max_rows, dim, cosine, tp, L.tiles_max, dzis, dzjs);
 }

@@ -76,9 +76,7 @@ extern "C" int rf_query_windows(const float* raw, int b, int s, int ps, int ctx,
     const int np = s / ps, w = ps + 2 * ctx;
     const size_t planes = (size_t)b * np * np * np * w;
     RF_REQUIRE(planes < (1ull << 31), RF_E_INVALID, "rf_query_windows: too many window planes (%zu)", planes);
-    hipLaunchKernelGGL(k_query_windows, dim3((unsigned)planes), dim3(256), 0, (hipStream_t)stream, raw, b, s, ps, ctx, pad_value, mean, stddev, out);
-    RF_CHECK_LAUNCH("rf_query_windows");
-    return RF_OK;
+    return rf_launch<k_query_windows>("rf_query_windows", dim3((unsigned)planes), dim3(256), (hipStream_t)stream, raw, b, s, ps, ctx, pad_value, mean, stddev, out);
 }
 
 // ---------------------------------------------------------------------------------------- windows of a feature grid
@@ -116,9 +114,7 @@ extern "C" int rf_gather_windows(const float* grid, int n, int c, int g, int w, 
     RF_REQUIRE(w <= 255, RF_E_INVALID, "rf_gather_windows: window edge %d", w);
     const size_t blocks = (size_t)n * np * np * np * c;
     RF_REQUIRE(blocks < (1ull << 31), RF_E_INVALID, "rf_gather_windows: too many (window, channel) pairs (%zu)", blocks);
-    hipLaunchKernelGGL(k_gather_windows<float>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, grid, n, c, g, w, step, np, out);
-    RF_CHECK_LAUNCH("rf_gather_windows");
-    return RF_OK;
+    return rf_launch<k_gather_windows<float>>("rf_gather_windows", dim3((unsigned)blocks), dim3(256), (hipStream_t)stream, grid, n, c, g, w, step, np, out);
 }
 
 // the same cut on a tensor in the valid convs' split form ([n][c/4][h | l][g^3] 8-byte slots): 2 c/4 planes of 8-byte voxels per sample
@@ -128,10 +124,8 @@ extern "C" int rf_gather_windows_split(const void* grid, int n, int c, int g, in
     RF_REQUIRE(w <= 255, RF_E_INVALID, "rf_gather_windows_split: window edge %d", w);
     const size_t blocks = (size_t)n * np * np * np * (c / 2);
     RF_REQUIRE(blocks < (1ull << 31), RF_E_INVALID, "rf_gather_windows_split: too many (window, channel pair) units (%zu)", blocks);
-    hipLaunchKernelGGL(k_gather_windows<double>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
-                       reinterpret_cast<const double*>(grid), n, c / 2, g, w, step, np, reinterpret_cast<double*>(out));
-    RF_CHECK_LAUNCH("rf_gather_windows_split");
-    return RF_OK;
+    return rf_launch<k_gather_windows<double>>("rf_gather_windows_split", dim3((unsigned)blocks), dim3(256), (hipStream_t)stream,
+                                               reinterpret_cast<const double*>(grid), n, c / 2, g, w, step, np, reinterpret_cast<double*>(out));
 }
 
 // ------------------------------------------------------------------------------------------------- DB packing
@@ -216,10 +210,9 @@ extern "C" int rf_db_pack_embeddings(const float* emb, int64_t n, int dim, float
     RF_REQUIRE(emb && packed && n > 0, RF_E_INVALID, "rf_db_pack_embeddings: bad arguments");
     RF_REQUIRE(dim == RF_DIM, RF_E_UNSUPPORTED, "rf_db_pack_embeddings: embedding dim %d (only 64, the latent_dim of every shipped config)", dim);
     const DbViews v = rf_db_views(packed, n);
-    const size_t want = ((size_t)(v.rows - v.blocked) + 255) / 256;     // a thread per float of the blocked view
-    hipLaunchKernelGGL(k_db_pack, dim3((unsigned)(want < 8192 ? want : 8192)), dim3(256), 0, (hipStream_t)stream, emb, (long long)n, v.blocked, v.rows, v.hd, v.rows16, v.hd16, v.rows16l);
-    RF_CHECK_LAUNCH("rf_db_pack_embeddings");
-    return RF_OK;
+    // a thread per float of the blocked view
+    return rf_launch<k_db_pack>("rf_db_pack_embeddings", dim3(rf_blocks((size_t)(v.rows - v.blocked), 256, 8192)), dim3(256), (hipStream_t)stream, emb, (long long)n,
+                                v.blocked, v.rows, v.hd, v.rows16, v.hd16, v.rows16l);
 }
 
 // --------------------------------------------------------------------------------------------------- the scans
@@ -957,9 +950,9 @@ extern "C" size_t rf_l2_topk_ws_bytes(int nq, int64_t n, int k2) {
 }
 
 template <int R>
-static void launch_merge_wave(const u64* parts, int nparts, int nq, int width, int k2, float* out_dist, long long* out_idx, u64* out_keys, const float* seed_q,
-                              const float* seed_rows, float* seed_t0, hipStream_t s) {
-    hipLaunchKernelGGL(k_merge_wave<R>, dim3((nq + 3) / 4), dim3(256), 0, s, parts, nparts, nq, width, k2, out_dist, out_idx, out_keys, seed_q, seed_rows, seed_t0);
+static int launch_merge_wave(const char* who, const u64* parts, int nparts, int nq, int width, int k2, float* out_dist, long long* out_idx, u64* out_keys,
+                             const float* seed_q, const float* seed_rows, float* seed_t0, hipStream_t s) {
+    return rf_launch<k_merge_wave<R>>(who, dim3((nq + 3) / 4), dim3(256), s, parts, nparts, nq, width, k2, out_dist, out_idx, out_keys, seed_q, seed_rows, seed_t0);
 }
 
 static int launch_merge(const u64* parts, int nparts, int nq, int width, int k2, float* out_dist, int64_t* out_idx, u64* out_keys, hipStream_t s,
@@ -968,14 +961,12 @@ static int launch_merge(const u64* parts, int nparts, int nq, int width, int k2,
     RF_REQUIRE(total <= 4096, RF_E_UNSUPPORTED, "%s: %d candidates per query exceed the merge capacity 4096", who, total);
     RF_REQUIRE(k2 >= 1 && k2 <= 64, RF_E_UNSUPPORTED, "%s: k2 = %d outside 1..64", who, k2);
     long long* oi = (long long*)out_idx;
-    if (total <= 128) launch_merge_wave<2>(parts, nparts, nq, width, k2, out_dist, oi, out_keys, seed_q, seed_rows, seed_t0, s);
-    else if (total <= 256) launch_merge_wave<4>(parts, nparts, nq, width, k2, out_dist, oi, out_keys, seed_q, seed_rows, seed_t0, s);
-    else if (total <= 512) launch_merge_wave<8>(parts, nparts, nq, width, k2, out_dist, oi, out_keys, seed_q, seed_rows, seed_t0, s);
-    else if (total <= 1024) launch_merge_wave<16>(parts, nparts, nq, width, k2, out_dist, oi, out_keys, seed_q, seed_rows, seed_t0, s);
-    else if (total <= 2048) launch_merge_wave<32>(parts, nparts, nq, width, k2, out_dist, oi, out_keys, seed_q, seed_rows, seed_t0, s);
-    else launch_merge_wave<64>(parts, nparts, nq, width, k2, out_dist, oi, out_keys, seed_q, seed_rows, seed_t0, s);
-    RF_CHECK_LAUNCH(who);
-    return RF_OK;
+    if (total <= 128) return launch_merge_wave<2>(who, parts, nparts, nq, width, k2, out_dist, oi, out_keys, seed_q, seed_rows, seed_t0, s);
+    if (total <= 256) return launch_merge_wave<4>(who, parts, nparts, nq, width, k2, out_dist, oi, out_keys, seed_q, seed_rows, seed_t0, s);
+    if (total <= 512) return launch_merge_wave<8>(who, parts, nparts, nq, width, k2, out_dist, oi, out_keys, seed_q, seed_rows, seed_t0, s);
+    if (total <= 1024) return launch_merge_wave<16>(who, parts, nparts, nq, width, k2, out_dist, oi, out_keys, seed_q, seed_rows, seed_t0, s);
+    if (total <= 2048) return launch_merge_wave<32>(who, parts, nparts, nq, width, k2, out_dist, oi, out_keys, seed_q, seed_rows, seed_t0, s);
+    return launch_merge_wave<64>(who, parts, nparts, nq, width, k2, out_dist, oi, out_keys, seed_q, seed_rows, seed_t0, s);
 }
 
 // Which scan (measured on MI355X, tools/topk_bench.py; k2 = 8): 2048 queries -- 50 k rows: VALU 0.47 ms / MFMA 0.59 ms, 125 k: 0.92 / 0.79,
@@ -1005,11 +996,8 @@ static TopkSlices topk_slices(long long units, int groups, int target_waves, lon
 }
 
 // the <8> / <16> fork of the list width
-#define RF_LAUNCH_K2(kern, k2p, grid, stream, ...)                                                   \
-    do {                                                                                             \
-        if ((k2p) == 8) hipLaunchKernelGGL(kern<8>, grid, dim3(256), 0, stream, __VA_ARGS__);        \
-        else hipLaunchKernelGGL(kern<16>, grid, dim3(256), 0, stream, __VA_ARGS__);                  \
-    } while (0)
+#define RF_LAUNCH_K2(who, kern, k2p, grid, stream, ...) \
+    ((k2p) == 8 ? rf_launch<kern<8>>(who, grid, dim3(256), stream, __VA_ARGS__) : rf_launch<kern<16>>(who, grid, dim3(256), stream, __VA_ARGS__))
 
 // workspace: [per-slice lists: 64 x nq x k2p keys][sample pass: nq x k2p (dist f32, idx i64)]
 // n_layout: the row count the packed image was built for (the offsets of its views depend on it); n <= n_layout: the rows scanned (the first n of the shard)
@@ -1039,7 +1027,7 @@ static int topk_impl(const float* q, int nq, int dim, const float* db_packed, in
         float* qc = reinterpret_cast<float*>(t_idx + (size_t)nq * k2p);
         if (f16_filter) {
             // the bound t0: k_l2_topk_seed16 + k_merge_wave (see there) over the shard's first rows
-            hipLaunchKernelGGL(k_query_chains, dim3((unsigned)(((size_t)nq * RF_DIM + 255) / 256)), dim3(256), 0, s, q, nq, qc);
+            if (int rc = rf_launch<k_query_chains>("rf_l2_topk(seed)", dim3((unsigned)(((size_t)nq * RF_DIM + 255) / 256)), dim3(256), s, q, nq, qc)) return rc;
             long long seed = n / (n <= 131072 ? TOPK_SEED_DIV : 4 * TOPK_SEED_DIV);
             if (seed < 2048) seed = 2048;
             seed = (seed + 63) / 64 * 64;
@@ -1047,11 +1035,13 @@ static int topk_impl(const float* q, int nq, int dim, const float* db_packed, in
             // 8 candidates per (slice, query) in the lists' workspace (64 k2p keys per query): at least 8 tiles per slice, ~2048 waves if possible
             const long long tiles = (seed + 31) / 32;
             const TopkSlices ss = topk_slices(tiles, qgroups, 2048, tiles / 8);
-            hipLaunchKernelGGL(k_l2_topk_seed16, dim3(ss.count, qtiles), dim3(256), 0, s, q, nq, v.rows16, v.rows16l, v.hd16, (long long)seed, (int)(ss.per * 32), parts);
-            RF_CHECK_LAUNCH("rf_l2_topk(seed)");
-            int rc = launch_merge(parts, ss.count, nq, 8, k2, nullptr, nullptr, nullptr, s, "rf_l2_topk(seed merge)", qc, v.rows, t_dist);
-            if (rc != RF_OK) return rc;
-            RF_LAUNCH_K2(k_l2_topk_mfma16, k2p, dim3(sl.count, qtiles), s, q, nq, v.rows, v.rows16, v.rows16l, v.hd16, (long long)n, (unsigned)row_base, rows_per_slice, t_dist, 1, parts, qc);
+            if (int rc = rf_launch<k_l2_topk_seed16>("rf_l2_topk(seed)", dim3(ss.count, qtiles), dim3(256), s, q, nq, v.rows16, v.rows16l, v.hd16, (long long)seed,
+                                                     (int)(ss.per * 32), parts))
+                return rc;
+            if (int rc = launch_merge(parts, ss.count, nq, 8, k2, nullptr, nullptr, nullptr, s, "rf_l2_topk(seed merge)", qc, v.rows, t_dist)) return rc;
+            if (int rc = RF_LAUNCH_K2("rf_l2_topk(mfma scan)", k_l2_topk_mfma16, k2p, dim3(sl.count, qtiles), s, q, nq, v.rows, v.rows16, v.rows16l, v.hd16, (long long)n,
+                                      (unsigned)row_base, rows_per_slice, t_dist, 1, parts, qc))
+                return rc;
         } else {
             // the bound t0 (algo 2, kept for comparison): exact top-k2p of the first n / TOPK_SAMPLE_DIV rows by this function itself (VALU scan, or nested
             // filtered scans for big samples); the k2-th best of query qi is t0[qi * k2p]
@@ -1060,17 +1050,17 @@ static int topk_impl(const float* q, int nq, int dim, const float* db_packed, in
             sample = (sample + 63) / 64 * 64;
             if (sample > n) sample = n;
             const int sample_algo = use_mfma_scan(nq, sample) ? 2 : 1;
-            int rc = topk_impl(q, nq, dim, db_packed, sample, n_layout, row_base, k2p, sample_algo, t_dist, t_idx, nullptr, ws, ws_bytes, stream);
-            if (rc != RF_OK) return rc;
-            RF_LAUNCH_K2(k_l2_topk_mfma, k2p, dim3(sl.count, qtiles), s, q, nq, v.rows, v.hd, (long long)n, (unsigned)row_base, rows_per_slice, t_dist + (k2 - 1), k2p, parts);
+            if (int rc = topk_impl(q, nq, dim, db_packed, sample, n_layout, row_base, k2p, sample_algo, t_dist, t_idx, nullptr, ws, ws_bytes, stream)) return rc;
+            if (int rc = RF_LAUNCH_K2("rf_l2_topk(mfma scan)", k_l2_topk_mfma, k2p, dim3(sl.count, qtiles), s, q, nq, v.rows, v.hd, (long long)n, (unsigned)row_base,
+                                      rows_per_slice, t_dist + (k2 - 1), k2p, parts))
+                return rc;
         }
-        RF_CHECK_LAUNCH("rf_l2_topk(mfma scan)");
     } else {
         // enough workgroups to fill 256 CUs a few times over, at least 4 blocks per list
         const int qtiles = (nq + RF_TQ - 1) / RF_TQ;
         sl = topk_slices(nblk, qtiles, 1024, (nblk + 3) / 4);
-        RF_LAUNCH_K2(k_l2_topk, k2p, dim3(sl.count, qtiles), s, q, nq, db_packed, (long long)n, (unsigned)row_base, (int)sl.per, parts);
-        RF_CHECK_LAUNCH("rf_l2_topk(scan)");
+        if (int rc = RF_LAUNCH_K2("rf_l2_topk(scan)", k_l2_topk, k2p, dim3(sl.count, qtiles), s, q, nq, db_packed, (long long)n, (unsigned)row_base, (int)sl.per, parts))
+            return rc;
     }
     // merge the per-slice lists (each k2p wide) and emit the first k2
     return launch_merge(parts, sl.count, nq, k2p, k2, out_dist, out_idx, out_keys, s, "rf_l2_topk(merge)");
@@ -1137,11 +1127,9 @@ extern "C" int rf_topk_merge(const float* in_dist, const int64_t* in_idx, int pa
     hipStream_t s = (hipStream_t)stream;
     const long long* idx = (const long long*)in_idx;
     long long* oidx = (long long*)out_idx;
-    if (total <= 256) hipLaunchKernelGGL(k_merge_pairs<256>, dim3(nq), dim3(256), 0, s, in_dist, idx, parts, nq, k2, out_dist, oidx);
-    else if (total <= 1024) hipLaunchKernelGGL(k_merge_pairs<1024>, dim3(nq), dim3(256), 0, s, in_dist, idx, parts, nq, k2, out_dist, oidx);
-    else hipLaunchKernelGGL(k_merge_pairs<4096>, dim3(nq), dim3(256), 0, s, in_dist, idx, parts, nq, k2, out_dist, oidx);
-    RF_CHECK_LAUNCH("rf_topk_merge");
-    return RF_OK;
+    if (total <= 256) return rf_launch<k_merge_pairs<256>>("rf_topk_merge", dim3(nq), dim3(256), s, in_dist, idx, parts, nq, k2, out_dist, oidx);
+    if (total <= 1024) return rf_launch<k_merge_pairs<1024>>("rf_topk_merge", dim3(nq), dim3(256), s, in_dist, idx, parts, nq, k2, out_dist, oidx);
+    return rf_launch<k_merge_pairs<4096>>("rf_topk_merge", dim3(nq), dim3(256), s, in_dist, idx, parts, nq, k2, out_dist, oidx);
 }
 
 // ---------------------------------------------------------------------------------------- same-scene demotion
@@ -1190,10 +1178,8 @@ extern "C" int rf_demote_same_scene(const float* dist, const int64_t* idx, int n
                                     int64_t* out_idx, void* stream) {
     RF_REQUIRE(dist && idx && db_meta && out_meta && out_dist && out_idx && nq > 0 && k2 > 0 && K > 0 && K <= k2, RF_E_INVALID,
                "rf_demote_same_scene: bad arguments (k2=%d K=%d)", k2, K);
-    hipLaunchKernelGGL(k_demote, dim3((nq + 255) / 256), dim3(256), 0, (hipStream_t)stream, dist, (const long long*)idx, nq, k2, db_meta,
-                       query_scene, query_keep, K, out_meta, out_dist, (long long*)out_idx);
-    RF_CHECK_LAUNCH("rf_demote_same_scene");
-    return RF_OK;
+    return rf_launch<k_demote>("rf_demote_same_scene", dim3((nq + 255) / 256), dim3(256), (hipStream_t)stream, dist, (const long long*)idx, nq, k2, db_meta,
+                               query_scene, query_keep, K, out_meta, out_dist, (long long*)out_idx);
 }
 
 // ------------------------------------------------------------------------------------------------ patch gather
@@ -1256,10 +1242,8 @@ static int gather_patches(const T* db_volumes, int64_t n_scenes, const int32_t* 
                           float stddev, int layout, float* out, void* stream, const char* who) {
     RF_REQUIRE(db_volumes && meta && out && chunks > 0 && K > 0 && n_scenes > 0, RF_E_INVALID, "%s: bad arguments", who);
     RF_REQUIRE(layout == 0 || layout == 1, RF_E_INVALID, "%s: layout %d", who, layout);
-    hipLaunchKernelGGL(k_gather_patches<T>, dim3((unsigned)chunks * K * 64), dim3(256), 0, (hipStream_t)stream, db_volumes, (long long)n_scenes, meta,
-                       K, trunc_fill, trunc_ratio, mean, stddev, layout, out);
-    RF_CHECK_LAUNCH(who);
-    return RF_OK;
+    return rf_launch<k_gather_patches<T>>(who, dim3((unsigned)chunks * K * 64), dim3(256), (hipStream_t)stream, db_volumes, (long long)n_scenes, meta, K, trunc_fill,
+                                          trunc_ratio, mean, stddev, layout, out);
 }
 
 extern "C" int rf_gather_patches(const float* db_volumes, int64_t n_scenes, const int32_t* meta, int chunks, int K,
@@ -1334,13 +1318,10 @@ extern "C" int rf_compose_overlap(const void* db_volumes, int half, int64_t n_sc
     RF_REQUIRE(db_volumes && mapping && boxes && out && dist_ws && n_scenes > 0 && P >= 0 && K > 0 && sx > 0 && sy > 0 && sz > 0, RF_E_INVALID,
                "rf_compose_overlap: bad arguments");
     if (half)
-        hipLaunchKernelGGL(k_compose_overlap<_Float16>, dim3((unsigned)K), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const _Float16*>(db_volumes),
-                           (long long)n_scenes, mapping, boxes, P, K, sx, sy, sz, trunc_fill, trunc_ratio, out, dist_ws);
-    else
-        hipLaunchKernelGGL(k_compose_overlap<float>, dim3((unsigned)K), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const float*>(db_volumes),
-                           (long long)n_scenes, mapping, boxes, P, K, sx, sy, sz, trunc_fill, trunc_ratio, out, dist_ws);
-    RF_CHECK_LAUNCH("rf_compose_overlap");
-    return RF_OK;
+        return rf_launch<k_compose_overlap<_Float16>>("rf_compose_overlap", dim3((unsigned)K), dim3(256), (hipStream_t)stream, reinterpret_cast<const _Float16*>(db_volumes),
+                                                      (long long)n_scenes, mapping, boxes, P, K, sx, sy, sz, trunc_fill, trunc_ratio, out, dist_ws);
+    return rf_launch<k_compose_overlap<float>>("rf_compose_overlap", dim3((unsigned)K), dim3(256), (hipStream_t)stream, reinterpret_cast<const float*>(db_volumes),
+                                               (long long)n_scenes, mapping, boxes, P, K, sx, sy, sz, trunc_fill, trunc_ratio, out, dist_ws);
 }
 
 // ------------------------------------------------------------------------------------------------- row gather
@@ -1358,7 +1339,5 @@ __global__ __launch_bounds__(256) void k_gather_rows(const float* __restrict__ s
 
 extern "C" int rf_gather_rows(const float* src, int64_t n_src, const int64_t* idx, int64_t m, int width, float* out, void* stream) {
     RF_REQUIRE(src && idx && out && n_src > 0 && m > 0 && width > 0 && (width & 3) == 0, RF_E_INVALID, "rf_gather_rows: bad arguments");
-    hipLaunchKernelGGL(k_gather_rows, dim3((unsigned)m), dim3(256), 0, (hipStream_t)stream, src, (long long)n_src, (const long long*)idx, width / 4, out);
-    RF_CHECK_LAUNCH("rf_gather_rows");
-    return RF_OK;
+    return rf_launch<k_gather_rows>("rf_gather_rows", dim3((unsigned)m), dim3(256), (hipStream_t)stream, src, (long long)n_src, (const long long*)idx, width / 4, out);
 }

@@ -251,10 +251,8 @@ extern "C" int rf_train_sobel_normals(const float* v, int n, int d, int h, int w
     const long long tiles = tiles_of(n, d, h, w, &g);
     RF_REQUIRE(tiles > 0, RF_E_UNSUPPORTED, "rf_train_sobel_normals: %d volumes of %d x %d x %d voxels (at most 2^31 - 1 voxels per volume and tiles per batch)", n,
                d, h, w);
-    hipLaunchKernelGGL(k_sobel_normals, dim3((unsigned)tiles), dim3(kThreads), 0, (hipStream_t)stream, v, g, scale, shift, pad, thr, w_occ_minus_1, normals,
-                       weights, empty);
-    RF_CHECK_LAUNCH("rf_train_sobel_normals");
-    return RF_OK;
+    return rf_launch<k_sobel_normals>("rf_train_sobel_normals", dim3((unsigned)tiles), dim3(kThreads), (hipStream_t)stream, v, g, scale, shift, pad, thr,
+                                      w_occ_minus_1, normals, weights, empty);
 }
 
 extern "C" size_t rf_train_shape_loss_ws_bytes(int n, int d, int h, int w) {
@@ -276,13 +274,11 @@ extern "C" int rf_train_shape_loss(const float* pred, const float* target, const
     RF_REQUIRE(ws_bytes >= need, RF_E_WORKSPACE, "rf_train_shape_loss: workspace of %zu bytes, needs %zu", ws_bytes, need);
     const int do_l1 = lambda_rec > 0.f, do_normal = lambda_n > 0.f;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_shape_loss, dim3((unsigned)tiles), dim3(kThreads), 0, s, pred, target, weights, empty, normals_t, g, trunc, mean, std, do_l1,
-                       do_normal, grad_l1, grad_g, reinterpret_cast<double*>(ws));
-    RF_CHECK_LAUNCH("rf_train_shape_loss");
-    hipLaunchKernelGGL(k_shape_loss_finish, dim3(1), dim3(256), 0, s, reinterpret_cast<const double*>(ws), (int)tiles, (double)n * d * h * w, lambda_rec,
-                       lambda_n, do_l1, do_normal, out, reinterpret_cast<long long*>(counts));
-    RF_CHECK_LAUNCH("rf_train_shape_loss (finish)");
-    return RF_OK;
+    if (int rc = rf_launch<k_shape_loss>("rf_train_shape_loss", dim3((unsigned)tiles), dim3(kThreads), s, pred, target, weights, empty, normals_t, g, trunc, mean, std,
+                                         do_l1, do_normal, grad_l1, grad_g, reinterpret_cast<double*>(ws)))
+        return rc;
+    return rf_launch<k_shape_loss_finish>("rf_train_shape_loss (finish)", dim3(1), dim3(256), s, reinterpret_cast<const double*>(ws), (int)tiles,
+                                          (double)n * d * h * w, lambda_rec, lambda_n, do_l1, do_normal, out, reinterpret_cast<long long*>(counts));
 }
 
 extern "C" int rf_train_shape_loss_backward(const float* grad_l1, const float* grad_g, const float* coef, const int64_t* counts, int n, int d, int h, int w,
@@ -292,8 +288,6 @@ extern "C" int rf_train_shape_loss_backward(const float* grad_l1, const float* g
     const long long tiles = tiles_of(n, d, h, w, &g);
     RF_REQUIRE(tiles > 0, RF_E_UNSUPPORTED,
                "rf_train_shape_loss_backward: %d volumes of %d x %d x %d voxels (at most 2^31 - 1 voxels per volume and tiles per batch)", n, d, h, w);
-    hipLaunchKernelGGL(k_shape_loss_bwd, dim3((unsigned)tiles), dim3(kThreads), 0, (hipStream_t)stream, grad_l1, grad_g, coef,
-                       reinterpret_cast<const long long*>(counts), g, trunc, (double)n * d * h * w, dpred);
-    RF_CHECK_LAUNCH("rf_train_shape_loss_backward");
-    return RF_OK;
+    return rf_launch<k_shape_loss_bwd>("rf_train_shape_loss_backward", dim3((unsigned)tiles), dim3(kThreads), (hipStream_t)stream, grad_l1, grad_g, coef,
+                                       reinterpret_cast<const long long*>(counts), g, trunc, (double)n * d * h * w, dpred);
 }

@@ -974,6 +974,23 @@ def test_conv3d_valid_leaky_lds(ops, spec):
     close(got, gather, 1e-5, 'lds form vs gather form')
 
 
+def test_conv3d_valid_leaky_lds_above_64k_in_growing_order(ops):
+    """Two layers on ONE instantiation (k_convv_lds<2, 2>) that plan more than the 64 KB of LDS a kernel gets without asking, the smaller plan first
+    (66,112 then 70,912 bytes): the opt-in limit is the instantiation's, not the first call's.  One test, not parametrised: the order inside the
+    process is the point.  Checks as test_conv3d_valid_leaky_lds (K = cin k^3 = 128)."""
+    for spec in [(1, 2, 43, 24, 4, 2), (1, 2, 24, 24, 4, 2)]:
+        n, cin, s, cout, k, stride = spec
+        gen = torch.Generator().manual_seed(sum(spec) + 2)
+        x, w, b = rnd(gen, n, cin, s, s, s), rnd(gen, cout, cin, k, k, k, scale=1 / np.sqrt(cin * k ** 3)), rnd(gen, cout)
+        xd = x.to(DEV)
+        assert ops.conv_valid_lds_supported(xd, cout, k, stride), spec
+        ref = F.leaky_relu(F.conv3d(x.double(), w.double(), b.double(), stride=stride), 0.2).float()
+        got = ops.conv3d_valid_leaky_lds(xd, ops.pack_convv_lds_weight(w.to(DEV)), b.to(DEV), cout, k, stride, 0.2)
+        close(got, ref, 1e-5, 'valid conv (lds) %s' % (spec,))
+        gather = ops.conv3d_valid_leaky_mfma(xd, ops.pack_convv_weight(w.to(DEV)), b.to(DEV), cout, k, stride, 0.2)
+        close(got, gather, 1e-5, 'lds form vs gather form %s' % (spec,))
+
+
 @pytest.mark.parametrize('spec', [(3, 1, 48, 12, 5), (2, 12, 44, 24, 3), (3, 1, 32, 8, 5), (2, 8, 28, 16, 3), (2, 1, 24, 12, 3), (3, 12, 22, 24, 3),
                                   (2, 1, 16, 16, 3), (5, 1, 13, 8, 3), (2, 12, 11, 24, 3)])
 def test_conv3d_valid_leaky_valu(ops, spec):

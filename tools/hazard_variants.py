@@ -18,7 +18,7 @@ FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wno-unused-fun
 
 SYNC_A = '        __syncthreads();                                   // everyone is done reading xs / ws[buf]; loads + DMA have landed\n'
 DMA = '                    __builtin_amdgcn_global_load_lds((rf_gptr)(src + off), (rf_lptr)(dst + q * 256), 16, 0, 0);\n'
-PFX = 'auto kern = k_conv3_mfma<TZ, TY, TX, SPW, NW, MB, NB, WPS, true, CCT>;'
+PFX = 'rf_launch<k_conv3_mfma<TZ, TY, TX, SPW, NW, MB, NB, WPS, true, CCT>>('      # launch_conv3: the kernel instantiation it launches
 COMMIT_STORE = '''                float* dst = xs + rowbox[i];
 #pragma unroll
                 for (int j = 0; j < TX + 2; ++j) dst[j] = v[j];
