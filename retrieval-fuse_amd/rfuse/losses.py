@@ -25,6 +25,16 @@ Then the contrastive term (csrc/ntxent.hip behind include/rfuse_contrastive.h), 
 The reference's sliced loss asks the host twice per slice whether and how many rows are occupied, boolean-indexes them and runs NTXentLoss on each slice in
 turn.  Here the selection is made on the device (the same greedy rule in slice order), the similarity matrix is never materialised, and nothing waits for the
 host: four launches forward, one backward.  The arithmetic is float64 from the float32 features on, the sums have one order: the same bits on every call.
+
+And the producer of that IoU matrix with the rest of the retrieval trainer's step (csrc/iou_matrix.hip behind include/rfuse_pairs.h), without a CPU fallback:
+
+    m = iou_matrix(occupancy)                                                                # util/misc.py get_iou_matrix: bool / uint8 [n,1,D,H,W] -> [n, n]
+    m = target_iou_matrix(batch['target'], target_mean, target_std, 0.75 * voxel_size)       # trainer/train_retrieval.py:85 with its .repeat(2, 2): [2B, 2B]
+    step = RetrievalStepLoss.from_config(cfg, temperature=0.2)                               # trainer/train_retrieval.py:77-88
+    total_loss, loss_contrastive = step(features_in, features_tgt, batch['target'], train=True)
+
+The reference materialises four [n^2, D, H, W] bool tensors; here a window becomes one bit per voxel and a pair one AND + popcount per 64 voxels.  The counts
+are integers and the four float32 operations after them are the reference's: the matrix has the reference's bits.
 """
 import torch
 
@@ -270,3 +280,128 @@ class AttnContrastiveLoss:
         loss, counts = _NTXentFn.apply(zis, zjs, occ, None, int(num_slices), self.max_rows, 1, _f32(self.temperature), 0.0, 0.0)
         self.last_counts = counts
         return loss
+
+
+# ------------------------------------------------------------------------------------------------ the retrieval trainer's IoU matrix and step
+_IOU_MAX_N, _IOU_MAX_VOXELS = 8192, 1 << 24      # the supported range of include/rfuse_pairs.h
+
+
+def _windows(t, what, dtypes):
+    """what a tensor says about itself, before the question where it lives"""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError('%s: expected a torch.Tensor' % what)
+    if t.dim() != 5 or t.shape[1] != 1 or t.numel() == 0:
+        raise ValueError('%s: expected a non-empty [n, 1, D, H, W] tensor, got %s' % (what, tuple(t.shape)))
+    if t.dtype not in dtypes:
+        raise TypeError('%s: expected %s, got %s' % (what, ' or '.join(str(d) for d in dtypes), t.dtype))
+    return t.detach()
+
+
+def _on_gpu(t, what):
+    if not t.is_cuda:
+        raise RuntimeError('%s: the IoU matrix is built on the GPU only (got a %s tensor); there is no CPU fallback' % (what, t.device))
+    return t.contiguous()
+
+
+def _pack(x, kind, scale, shift, thr, other_n):
+    """one launch: (bits int64 [n, ceil(voxels / 64)], counts int32 [n]) of the windows ``x``"""
+    n, voxels = x.shape[0], x[0].numel()
+    lib = _lib.load_pairs()
+    if int(lib.rf_iou_ws_bytes(n, other_n, voxels)) == 0:
+        raise ValueError('iou_matrix: %d x %d samples of %d voxels is outside the supported range (1 <= samples <= %d, voxels <= %d)'
+                         % (n, other_n, voxels, _IOU_MAX_N, _IOU_MAX_VOXELS))
+    bits = torch.empty((n, (voxels + 63) // 64), dtype=torch.int64, device=x.device)
+    counts = torch.empty(n, dtype=torch.int32, device=x.device)
+    lib.rf_iou_pack(_p(x), kind, scale, shift, thr, n, voxels, _p(bits), _p(counts), _stream())
+    return bits, counts, voxels
+
+
+def _pairs(a, b, voxels, repeat):
+    if repeat not in (1, 2):
+        raise ValueError('iou_matrix: repeat is 1 or 2, got %r' % (repeat,))
+    (bits_a, counts_a), (bits_b, counts_b) = a, (b if b is not None else (None, None))
+    n_a, n_b = counts_a.numel(), counts_a.numel() if b is None else counts_b.numel()
+    out = torch.empty((repeat * n_a, repeat * n_b), dtype=torch.float32, device=bits_a.device)
+    _lib.load_pairs().rf_iou_matrix(_p(bits_a), _p(counts_a), n_a, _p(bits_b), _p(counts_b), n_b, voxels, repeat, _p(out), _stream())
+    return out
+
+
+@_device_scoped
+@torch.no_grad()
+def iou_matrix(batch_shapes, other=None, repeat=1):
+    """``util.misc.get_iou_matrix`` (util/misc.py:51-59) on the device: ``batch_shapes`` bool / uint8 [n, 1, D, H, W], non-zero = occupied; float32 [n, n] =
+    intersection / (union + 1e-5) of every pair of windows, the reference's bits.  With ``other`` ([m, 1, D, H, W], the same window) the [n, m] matrix of
+    the two sets; ``repeat=2`` returns what ``.repeat(2, 2)`` would.  Two launches (three with ``other``) on the current stream, nothing waits for the host,
+    and no [n^2, D, H, W] tensor exists."""
+    a = _windows(batch_shapes, 'iou_matrix: batch_shapes', (torch.bool, torch.uint8))
+    if other is None:
+        bits, counts, voxels = _pack(_on_gpu(a, 'iou_matrix: batch_shapes'), 0, 0.0, 0.0, 0.0, a.shape[0])
+        return _pairs((bits, counts), None, voxels, repeat)
+    b = _windows(other, 'iou_matrix: other', (torch.bool, torch.uint8))
+    if b.shape[2:] != a.shape[2:]:
+        raise ValueError('iou_matrix: other has windows of %s, batch_shapes of %s' % (tuple(b.shape[2:]), tuple(a.shape[2:])))
+    bits_a, counts_a, voxels = _pack(_on_gpu(a, 'iou_matrix: batch_shapes'), 0, 0.0, 0.0, 0.0, b.shape[0])
+    bits_b, counts_b, _ = _pack(_on_gpu(b, 'iou_matrix: other'), 0, 0.0, 0.0, 0.0, a.shape[0])
+    return _pairs((bits_a, counts_a), (bits_b, counts_b), voxels, repeat)
+
+
+@_device_scoped
+@torch.no_grad()
+def target_iou_matrix(target, target_mean, target_std, threshold, repeat=2):
+    """The trainer's ``get_iou_matrix(denormalize_target(batch['target']) <= threshold).repeat(2, 2)`` (trainer/train_retrieval.py:85) from the normalised
+    float32 targets [B, 1, D, H, W]: a voxel is occupied iff ``target * target_std + target_mean <= threshold`` in float32, operation by operation.
+    ``repeat=2``: the [2B, 2B] matrix that ``NTXent`` takes, written once."""
+    t = _on_gpu(_windows(target, 'target_iou_matrix: target', (torch.float32,)), 'target_iou_matrix: target')
+    bits, counts, voxels = _pack(t, 1, _f32(target_std), _f32(target_mean), _f32(threshold), t.shape[0])
+    return _pairs((bits, counts), None, voxels, repeat)
+
+
+class RetrievalStepLoss:
+    """The tail of ``RetrievalTrainingModule.step`` (trainer/train_retrieval.py:77-88): the two encoders' feature volumes through ``reshape_features``
+    (permute / reshape and F.normalize, in torch and differentiable), the code noise of a training step, the IoU matrix of the batch's targets when
+    ``iou_scaling`` is set, and ``NTXent(temperature, True)``.  Returns ``(total_loss, loss_contrastive)``; gradients flow to the two feature tensors only."""
+
+    def __init__(self, temperature, target_mean, target_std, voxel_size_target, iou_scaling=True, contrastive_weight=1.0, code_noise=0.0):
+        self.temperature, self.target_mean, self.target_std = temperature, float(target_mean), float(target_std)
+        self.threshold = 0.75 * voxel_size_target
+        self.iou_scaling, self.contrastive_weight, self.code_noise = bool(iou_scaling), contrastive_weight, code_noise
+        self.ntxent = NTXent(temperature, True)
+
+    @classmethod
+    def from_config(cls, config, **retrieval_training):
+        """``config``: an rfuse.configs dictionary or the reference's own (dataset_train carries target_mean, target_std and the raw voxel_size_target);
+        ``retrieval_training``: the constructor's keywords, or the reference's ``retrieval_training`` section as it stands (``temprature``, ``iou_scaling``,
+        ``loss: {contrastive: w}``, ``code_noise``; its other keys belong to the optimiser and the loader)."""
+        d, rt = config['dataset_train'], dict(retrieval_training)
+        if 'temprature' in rt:
+            rt['temperature'] = rt.pop('temprature')
+        if 'loss' in rt:
+            rt['contrastive_weight'] = rt.pop('loss')['contrastive']
+        if 'temperature' not in rt:
+            raise TypeError('RetrievalStepLoss.from_config: the temperature is missing')
+        keep = {k: rt[k] for k in ('iou_scaling', 'contrastive_weight', 'code_noise') if k in rt}
+        return cls(rt['temperature'], d['target_mean'], d['target_std'], d['voxel_size_target'], **keep)
+
+    @staticmethod
+    def reshape_features(feats):
+        feature_dim = feats.shape[1]
+        return torch.nn.functional.normalize(feats.permute((0, 2, 3, 4, 1)).reshape((-1, feature_dim)), dim=1)
+
+    def __call__(self, features_in, features_tgt, target, train=False):
+        for t, what in ((features_in, 'features_in'), (features_tgt, 'features_tgt')):
+            if not isinstance(t, torch.Tensor):
+                raise TypeError('RetrievalStepLoss: %s: expected a torch.Tensor' % what)
+            if t.dim() != 5:
+                raise ValueError('RetrievalStepLoss: %s: expected a [B, dim, d, h, w] tensor, got %s' % (what, tuple(t.shape)))
+            if not t.is_cuda:
+                raise RuntimeError('RetrievalStepLoss: %s: the step loss runs on the GPU only (got a %s tensor); there is no CPU fallback' % (what, t.device))
+        if not self.contrastive_weight > 0:              # the reference's zeros(1), times the weight
+            zero = torch.zeros(1, dtype=torch.float32, device=features_in.device)
+            return zero * self.contrastive_weight, zero
+        zis, zjs = self.reshape_features(features_in), self.reshape_features(features_tgt)
+        if train and self.code_noise > 0:
+            zis = zis + torch.empty_like(zis).normal_(mean=0, std=self.code_noise)
+            zjs = zjs + torch.empty_like(zjs).normal_(mean=0, std=self.code_noise)
+        iou = target_iou_matrix(target, self.target_mean, self.target_std, self.threshold, repeat=2) if self.iou_scaling else None
+        loss_contrastive = self.ntxent(zis, zjs, iou)
+        return loss_contrastive * self.contrastive_weight, loss_contrastive
