@@ -13,6 +13,8 @@ Sharding: rank g scans rows [g*N/W, (g+1)*N/W) for ALL queries an
 The voxel store is replicated (1 M patches = 15 625 chunks = 16.4 GB fp32, trivial against 288 GB), so no payload
 exchange is needed.
 """
+import weakref
+
 import torch
 
 from . import ops
@@ -294,6 +296,7 @@ class PatchDatabase:
         self.volumes = vols.to(self.device, torch.float16 if half_store else torch.float32).contiguous()
         self.n_scenes = self.volumes.shape[0]
         self.feature_cache = None        # see build_feature_cache
+        self._feature_cache_of = None    # (weak reference, version) of every backbone parameter the cache was computed from
 
     @torch.no_grad()
     def build_feature_cache(self, retrieval_backbone, config, rows_per_batch=4096):
@@ -320,7 +323,16 @@ class PatchDatabase:
                 feats = torch.empty((n,) + tuple(f.shape[1:]), dtype=torch.float32, device=self.device)
             feats[lo:hi] = f
         self.feature_cache = feats
+        self._feature_cache_of = [(weakref.ref(p), p._version) for p in retrieval_backbone.parameters()]
         return feats
+
+    def feature_cache_fresh(self, retrieval_backbone):
+        """True when ``feature_cache`` holds the features THIS backbone computes now: it was built from these very Parameter objects and none of them has been
+        modified in place since (an optimiser step, load_state_dict).  The caller keeps the parameters alive, so their identity cannot be re-used."""
+        if self.feature_cache is None or self._feature_cache_of is None:
+            return False
+        params = list(retrieval_backbone.parameters())
+        return len(params) == len(self._feature_cache_of) and all(r() is p and v == p._version for (r, v), p in zip(self._feature_cache_of, params))
 
     def local_topk(self, q, k2):
         """Exact squared-L2 top-k2 of q against this rank's shard, global row ids -> (dist, idx)."""

@@ -169,6 +169,9 @@ class RefinementEngine:
         if use_feature_cache:
             if self.database.feature_cache is None:
                 raise RuntimeError('use_feature_cache=True needs database.build_feature_cache(retrieval_backbone, config) first')
+            if not self.database.feature_cache_fresh(self.retrieval_backbone):
+                raise RuntimeError('use_feature_cache=True: the retrieval backbone\'s parameters have changed since the cache was built (or it was built from '
+                                   'another backbone); call database.build_feature_cache(retrieval_backbone, config) again')
             b = input_raw.shape[0]
             keep = patch_mask.reshape(-1).contiguous() if patch_mask is not None else None
             _, _, idx = self.database.retrieve(q, self.K, query_scene, keep)                # [B*64, K] database row ids; -1 (none) gathers the sentinel row

@@ -90,18 +90,25 @@ class PackedWeight:
         self.kind = kind        # a key of _PACKERS (end of this module)
         self._pack = _PACKERS[kind]
         self._key = None
+        self._of = None         # weak reference to the tensor object the image was packed from (see _same_objects)
         self._packed = None
         self._ready = _PackedReady()
 
     def get(self, w, *extra):
         key = (w.data_ptr(), w._version, tuple(w.shape), w.device) + extra
-        if key != self._key:
+        if key != self._key or self._of() is not w:
             self._packed = self._pack(w, *extra)
-            self._key = key
+            self._key, self._of = key, weakref.ref(w)
             self._ready.packed_on(w.device)
         else:
             self._ready.wait(w.device, self._packed)
         return self._packed
+
+
+def _same_objects(refs, tensors):
+    """the weak references of a pack key still point at these very tensor objects.  (address, version, shape, device) alone cannot tell a replaced
+    Parameter from the one an image was packed from: a new one on a re-used block has the old address and may have reached the old version count."""
+    return refs is not None and len(refs) == len(tensors) and all(r() is t for r, t in zip(refs, tensors))
 
 
 class _PackedReady:
@@ -313,36 +320,37 @@ CONV_ARITH = 'split'
 # A layer outside the range runs the fp32 kernels (model/unet.py:SingleConv) -- same results as the reference's fp32 path, no clamp.
 SPLIT_MAX_ABS_WEIGHT = 65504.0 / 16 / 8
 SPLIT_MAX_ABS_ACT = 65504.0 * 16
-_range_cache = {}                       # (data_ptr, shape, device) -> (version, max |t|)
 _range_seen = weakref.WeakValueDictionary()     # id -> every tensor whose range was asked for (the parameters of the networks in use)
 
 
-def _range_key(t):
-    return (t.data_ptr(), tuple(t.shape), t.device)
+def _fresh_range(t):
+    """max |t| as it was last computed for THIS tensor object, if ``t`` has not been modified in place or moved since; else None.  The value lives on
+    the object (``t._rf_range = (version, data_ptr, device, max |t|)``, like ``_rf_stats`` of the activations) and so dies with it: a later tensor at the
+    same address, with the same shape and version count (the caching allocator hands a freed block straight back), starts without one."""
+    hit = getattr(t, '_rf_range', None)
+    if hit is not None and hit[0] == t._version and hit[1] == t.data_ptr() and hit[2] == t.device:
+        return hit[3]
+    return None
 
 
 def _abs_max(t):
-    """max |t| of a parameter, cached per parameter version.  A training step changes every parameter at once (the optimiser's step): the
-    first miss after it refreshes ALL the parameters seen so far on that device in one ``torch._foreach_norm`` and one host sync, instead
-    of one sync per parameter (three per layer)."""
-    key = _range_key(t)
-    hit = _range_cache.get(key)
-    if hit is not None and hit[0] == t._version:
-        return hit[1]
+    """max |t| of a parameter, cached per parameter version on the parameter object.  A training step changes every parameter at once (the
+    optimiser's step): the first miss after it refreshes ALL the parameters seen so far on that device in one ``torch._foreach_norm`` and one
+    host sync, instead of one sync per parameter (three per layer)."""
+    hit = _fresh_range(t)
+    if hit is not None:
+        return hit
     if t.is_cuda and torch.cuda.is_current_stream_capturing():
         raise RuntimeError('range check of a parameter inside a graph capture: run one step before capturing (RefinementEngine.capture_graph does)')
-    if len(_range_cache) > 8192:
-        _range_cache.clear()
     _range_seen[id(t)] = t
-    stale = [u for u in list(_range_seen.values())
-             if u.device == t.device and u.dtype == t.dtype and u.numel() > 0 and _range_cache.get(_range_key(u), (None,))[0] != u._version]
+    stale = [u for u in list(_range_seen.values()) if u.device == t.device and u.dtype == t.dtype and u.numel() > 0 and _fresh_range(u) is None]
     if t.is_cuda and len(stale) > 1:
         vals = torch.stack(torch._foreach_norm([u.detach() for u in stale], float('inf'))).tolist()       # one host sync
         for u, val in zip(stale, vals):
-            _range_cache[_range_key(u)] = (u._version, float(val))
-        return _range_cache[key][1]
+            u._rf_range = (u._version, u.data_ptr(), u.device, float(val))
+        return t._rf_range[3]
     v = float(t.detach().abs().max().item())                                  # one host sync
-    _range_cache[key] = (t._version, v)
+    t._rf_range = (t._version, t.data_ptr(), t.device, v)
     return v
 
 
@@ -987,17 +995,18 @@ class PackedAttnMLP:
 
     def __init__(self):
         self._key = None
+        self._of = None
         self._packed = None
         self._ready = _PackedReady()
 
     def get(self, layers):
         params = [t for l in layers for t in (l.weight, l.bias)]
         key = tuple((t.data_ptr(), t._version, tuple(t.shape), t.device) for t in params)
-        if key != self._key:
+        if key != self._key or not _same_objects(self._of, params):
             img, split = pack_attn_mlp(params)
             if not all(split_range_ok(w) for w in params[0::2]):
                 split = None                                           # a weight outside the f16 pair's range: the fp32-MFMA form runs (no clamp)
-            self._packed, self._key = (img, split), key
+            self._packed, self._key, self._of = (img, split), key, tuple(weakref.ref(t) for t in params)
             self._ready.packed_on(params[0].device)
         else:
             self._ready.wait(params[0].device, self._packed)
