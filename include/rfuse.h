@@ -467,7 +467,9 @@ size_t rf_db_packed_floats(int64_t n, int dim);
  * global row id.  algo: 0 = pick by shard size, 1 = VALU scan (every pair evaluated exactly), 2 / 3 = MFMA-filtered scan
  * (matrix-core dot products -- 2: fp32 inputs, 3: inputs split into two f16 pieces, the same 2^-15 margin -- discard the pairs
  * that provably cannot enter a list, the rest is evaluated exactly in fp32): all return the same bits.
- * out_dist [nq][k2] float32, out_idx [nq][k2] int64 (global ids); missing candidates (n < k2): dist=+inf, idx=-1. */
+ * out_dist [nq][k2] float32, out_idx [nq][k2] int64 (global ids); missing candidates (n < k2): dist=+inf, idx=-1.
+ * Non-finite input: a +inf distance sorts behind every finite one and a NaN distance behind +inf, NaN candidates among themselves by row id (a NaN is returned
+ * as 0x7FC00000); every algo returns the same lists, and a query with an infinite or NaN component changes no other query's. */
 int rf_l2_topk(const float* q, int nq, int dim, const float* db_packed, int64_t n, int64_t row_base, int k2, int algo,
                float* out_dist, int64_t* out_idx, void* ws, size_t ws_bytes, void* stream);
 size_t rf_l2_topk_ws_bytes(int nq, int64_t n, int k2);
@@ -511,7 +513,7 @@ int rf_gather_patches_f16(const void* db_volumes_f16, int64_t n_scenes, const in
 /* create_retrieval_from_mapping for an OVERLAPPING patch grid of one scene (util/retrieval.py:145-164 with dataset.no_overlap False; :156: a patch overwrites its box of
  * retrieval k only while the mean of the distances stored there is above its own).  mapping [P][K][8] float32 rows (scene index, X0, X1, Y0, Y1, Z0, Z1, distance) of the
  * P patches patch_from_scene_lookup holds, in its order; boxes [P][6] int32 their unpadded target boxes (xx0, xx1, yy0, yy1, zz0, zz1) in the scene; db_volumes
- * [n_scenes][64^3] float32 (half = 0) or float16 (half = 1); out, dist_ws [K][sx][sy][sz] float32 (dist_ws: workspace).  Sequential over the patches by construction. */
+ * [n_scenes][64^3] float32 (half = 0) or float16 (half = 1); out, dist_ws [K][sx][sy][sz] float32 (dist_ws: workspace).  Sequential over the patches by construction.  P = 0 (mapping and boxes may be null): all trunc_fill. */
 int rf_compose_overlap(const void* db_volumes, int half, int64_t n_scenes, const float* mapping, const int32_t* boxes, int P, int K, int sx, int sy, int sz,
                        float trunc_fill, float trunc_ratio, float* out, float* dist_ws, void* stream);
 

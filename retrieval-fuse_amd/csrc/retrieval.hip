@@ -24,7 +24,12 @@
 typedef unsigned long long u64;
 #define RF_KEY_NONE 0xFFFFFFFFFFFFFFFFull
 
-__device__ __forceinline__ u64 make_key(float dist, unsigned row) { return ((u64)__float_as_uint(dist) << 32) | row; }
+// (a distance is >= +0, so its bits are at most +inf's 0x7F800000; whatever sign and payload the arithmetic left on a NaN -- a negated operand flips the sign --
+// the key holds the quiet NaN 0x7FC00000: NaN candidates sort behind +inf, among themselves by row id alone.  One unsigned minimum.)
+__device__ __forceinline__ u64 make_key(float dist, unsigned row) {
+    const unsigned b = __float_as_uint(dist);
+    return ((u64)(b < 0x7FC00000u ? b : 0x7FC00000u) << 32) | row;
+}
 
 // ---------------------------------------------------------------------------------------------- query windows
 // One workgroup per (window, w0) plane, a wave per output ROW (w consecutive elements along the last axis; the element-per-thread form of rounds 1-5
@@ -134,9 +139,10 @@ extern "C" int rf_gather_windows_split(const void* grid, int n, int c, int g, in
 //   rows     [n32][64], n32 = n rounded up to 32   the MFMA scan's A operand: position 16*g + m of a row holds dim 4*m + g, so
 //                                                the 64 contiguous bytes lane (row, g) loads are the dims {4m + g} = the g-th
 //                                                summation chain of the exact distance ("THE exact distance" at the scans, rf_chain16)
-//   hd       [n32]                               (1 - 2^-15) * |row|^2 / 2, +inf for the padding rows (they never pass the filter)
+//   hd       [n32]                               (1 - 2^-15) * |row|^2 / 2, +inf for the padding rows (they never pass the filter); -inf for a row with an infinite
+//                                                or NaN component (always re-checked: "non-finite input" at topk_prologue)
 //   rows16   [n32][64] f16                       the rows rounded to f16, natural dim order: A operands of the f16-filtered scan (the h pieces)
-//   hd16     [n32]                               (1 - 2^-15) * |row|^2 / 2; -inf for a row with a component beyond the f16 range (always re-checked)
+//   hd16     [n32]                               (1 - 2^-15) * |row|^2 / 2; -inf for a row with a component beyond the f16 range or not finite (always re-checked)
 //   rows16l  [n32][64] f16                       the l pieces: (x - h) * 2^11 rounded to f16 -- x = h + l / 2^11 up to 2^-22 |x| (round 6: the filter multiplies
 //                                                split operands, so that it is as tight as the fp32-MFMA filter at a fifth of its matrix-pipe cycles)
 #define RF_DIM 64
@@ -193,8 +199,9 @@ __global__ __launch_bounds__(256) void k_db_pack(const float* __restrict__ emb, 
         if (row < n) {
             double nd = 0.0, big = 0.0;
             for (int d = 0; d < RF_DIM; ++d) { const double v = emb[(size_t)row * RF_DIM + d]; nd += v * v; big = fmax(big, fabs(v)); }
-            h = (float)((1.0 - (double)RF_EPS_FILTER) * 0.5 * nd);
-            h16 = big < (double)RF_F16_RANGE ? (float)((1.0 - (double)RF_EPS_FILTER) * 0.5 * nd) : -INFINITY;
+            const bool finite = nd < (double)INFINITY;               // (a sum of 64 float squares cannot overflow a double) false for a row with an infinite or NaN component
+            h = finite ? (float)((1.0 - (double)RF_EPS_FILTER) * 0.5 * nd) : -INFINITY;
+            h16 = finite && big < (double)RF_F16_RANGE ? h : -INFINITY;
         }
         hd[row] = h;
         hd16[row] = h16;
@@ -395,7 +402,9 @@ __device__ __forceinline__ void slice_rows(int slice, int rows_per_slice, long l
 
 // The lists start EMPTY below a threshold: t0[q] is an upper bound of query q's final k2-th distance (+inf: none), so only pairs with distance <= t0 can matter.
 // algo 3 (F16): the seed's bound (k_l2_topk_seed16 + k_merge_wave).  algo 2: the k2-th best exact distance of rf_l2_topk's nested sample pass over the shard's
-// first rows.  h_q = (1 - eps) |q|^2 / 2, a_q = h_q - t0 / 2; F16: a query with a component beyond the f16 range has h_q = a_q = -inf (everything is re-checked).
+// first rows.  h_q = (1 - eps) |q|^2 / 2, a_q = h_q - t0 / 2; a query with an infinite or NaN component -- F16: or one beyond the f16 range -- has h_q = a_q = -inf
+// (everything is re-checked), and so has every such row (hd = -inf, k_db_pack).  A NaN distance is a key like any other (it sorts behind +inf, by row id): the
+// lists every scan returns for non-finite input are those of the VALU scan, which keys every pair.
 // The caller's wave_barrier + s_waitcnt make the LDS writes visible.
 template <int K2, bool F16>
 __device__ __forceinline__ void topk_prologue(const float* __restrict__ q, int nq, int q0, const float* __restrict__ t0, int t0_stride, u64* lists, float* aqs,
@@ -407,9 +416,13 @@ __device__ __forceinline__ void topk_prologue(const float* __restrict__ q, int n
         float nqn = 0.f, big = 0.f;
 #pragma unroll
         for (int d = 0; d < RF_DIM; ++d) { nqn = fmaf(qp[d], qp[d], nqn); big = fmaxf(big, fabsf(qp[d])); }
-        hq = !F16 || big < RF_F16_RANGE ? (1.f - RF_EPS_FILTER) * 0.5f * nqn : -INFINITY;
+        // non-finite input: |q|^2 is +inf or NaN exactly when a component is (fmaxf drops a NaN, so `big` cannot tell) -- such a query is not filtered at all
+        // (h_q = a_q = -inf, the 'beyond the f16 range' route), and a NaN bound (fewer than k2 rows behind it with a distance that is a number) is no bound
+        const bool filtered = nqn < INFINITY && (!F16 || big < RF_F16_RANGE);
+        hq = filtered ? (1.f - RF_EPS_FILTER) * 0.5f * nqn : -INFINITY;
         t = t0[(size_t)qi * t0_stride];
-        a = hq - 0.5f * t;                                           // t = +inf (fewer than k2 rows behind the bound): -inf, everything passes
+        t = t == t ? t : INFINITY;
+        a = filtered ? hq - 0.5f * t : -INFINITY;                    // t = +inf (fewer than k2 rows behind the bound): -inf, everything passes
     }
     hqs[lane] = hq;
     aqs[lane] = a;
@@ -424,7 +437,7 @@ __device__ __forceinline__ void topk_offer(u64* lists, float* aqs, const float* 
     u64 e = lane < K2 ? lists[ql * K2 + lane] : RF_KEY_NONE;
     const unsigned wlo = __builtin_amdgcn_readlane((unsigned)(e & 0xffffffffu), K2 - 1);
     const unsigned whi = __builtin_amdgcn_readlane((unsigned)(e >> 32), K2 - 1);
-    if (key < (((u64)whi << 32) | wlo) && dist <= t0s[ql]) {         // (<=: the row that set the bound must get in)
+    if (key < (((u64)whi << 32) | wlo) && !(dist > t0s[ql])) {       // (not above: the row that set the bound must get in, and so must a NaN distance)
         list_insert<K2>(e, lane, key);
         if (lane < K2) lists[ql * K2 + lane] = e;
         if (lane == K2 - 1) {                                        // T = min(bound, the list's k2-th distance once it is full)
@@ -506,7 +519,7 @@ __global__ __launch_bounds__(256, 2) void k_l2_topk_mfma(const float* __restrict
 #pragma unroll
             for (int nb = 0; nb < 4; ++nb)
 #pragma unroll
-                for (int i = 0; i < 4; ++i) anyhit |= __ballot(acc[mb][nb][i] >= aq[nb]);
+                for (int i = 0; i < 4; ++i) anyhit |= __ballot(!(acc[mb][nb][i] < aq[nb]));      // (not below: an infinite or NaN operand makes the product NaN)
         if (anyhit == 0ull) return;
         unsigned m = 0u;                                              // bit (mb*4 + nb)*4 + i: D row 4*lg + i of m-block mb, query column li of n-block nb
 #pragma unroll
@@ -514,7 +527,7 @@ __global__ __launch_bounds__(256, 2) void k_l2_topk_mfma(const float* __restrict
 #pragma unroll
             for (int nb = 0; nb < 4; ++nb)
 #pragma unroll
-                for (int i = 0; i < 4; ++i) m |= (acc[mb][nb][i] >= aq[nb] ? 1u : 0u) << ((mb * 4 + nb) * 4 + i);
+                for (int i = 0; i < 4; ++i) m |= (!(acc[mb][nb][i] < aq[nb]) ? 1u : 0u) << ((mb * 4 + nb) * 4 + i);
         // ---- some pair passed the filter: exact re-check from the registers that hold it
 #pragma unroll
         for (int mb = 0; mb < 2; ++mb)
@@ -927,6 +940,7 @@ __global__ __launch_bounds__(256) void k_merge_wave(const u64* __restrict__ part
                 const float4* xp = reinterpret_cast<const float4*>(seed_rows + (size_t)(unsigned)(mine & 0xffffffffu) * RF_DIM);
                 const float4* qp = reinterpret_cast<const float4*>(seed_q + (size_t)qi * RF_DIM);
                 dist = rf_chain_sum(rf_chain16(qp, xp), rf_chain16(qp + 4, xp + 4), rf_chain16(qp + 8, xp + 8), rf_chain16(qp + 12, xp + 12));
+                dist = dist == dist ? dist : INFINITY;               // a NaN distance sorts behind +inf: with such a row among the k2 there is no bound
             }
         }
         dist = wave_max(dist);
@@ -1315,7 +1329,8 @@ __global__ __launch_bounds__(256) void k_compose_overlap(const T* __restrict__ v
 
 extern "C" int rf_compose_overlap(const void* db_volumes, int half, int64_t n_scenes, const float* mapping, const int32_t* boxes, int P, int K, int sx, int sy, int sz,
                                   float trunc_fill, float trunc_ratio, float* out, float* dist_ws, void* stream) {
-    RF_REQUIRE(db_volumes && mapping && boxes && out && dist_ws && n_scenes > 0 && P >= 0 && K > 0 && sx > 0 && sy > 0 && sz > 0, RF_E_INVALID,
+    // (P = 0: a scene without patches is all truncation fill; there is no mapping or box to point at)
+    RF_REQUIRE(db_volumes && (P == 0 || (mapping && boxes)) && out && dist_ws && n_scenes > 0 && P >= 0 && K > 0 && sx > 0 && sy > 0 && sz > 0, RF_E_INVALID,
                "rf_compose_overlap: bad arguments");
     if (half)
         return rf_launch<k_compose_overlap<_Float16>>("rf_compose_overlap", dim3((unsigned)K), dim3(256), (hipStream_t)stream, reinterpret_cast<const _Float16*>(db_volumes),

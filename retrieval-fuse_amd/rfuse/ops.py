@@ -1274,7 +1274,9 @@ def compose_overlap(db_volumes, mapping, boxes, K, size, trunc_fill, trunc_ratio
 
 def paste_chunks(df, sel, dst, sx, sy, flat, round_half=True):
     """combine_predictions on the device: chunks ``sel`` (int32, indices into the refined batch df [b, 1, 64, 64, 64]) -> float16 rounding -> float64 ->
-    ``flat`` (float64) at element offsets ``dst`` (int64) with canvas strides sx, sy (reference dataset/patched_scene_dataset.py:160-186)."""
+    ``flat`` (float64) at element offsets ``dst`` (int64) with canvas strides sx, sy (reference dataset/patched_scene_dataset.py:160-186).  The offsets and the
+    strides must be EVEN: the kernel stores pairs of doubles (16 bytes); rfuse/scene.py's plans are even by construction (canvas extents are multiples of 64)
+    and odd strides are refused."""
     _req(df, 'df'), _req(sel, 'sel', torch.int32), _req(dst, 'dst', torch.int64), _req(flat, 'flat', torch.float64)
     if tuple(df.shape[1:]) != (1, 64, 64, 64) or sel.numel() != dst.numel():
         raise ValueError('paste_chunks: df must be [b, 1, 64, 64, 64] and sel / dst of one length (got %s, %d, %d)' % (tuple(df.shape), sel.numel(), dst.numel()))

@@ -3,7 +3,7 @@
 all-gather of the keys, per-rank merge, same-scene demotion -- gives every rank exactly the single-process result.
 
 The scan / merge / demotion kernels are replaced AT THE BACKEND SEAM (rfuse.database.HipSearchBackend) by numpy stand-ins
-with the same contracts (test infrastructure, defined here), so what runs on the CPU is the product's own wiring that runs
+with the same contracts (test infrastructure: tests/search_ref.py), so what runs on the CPU is the product's own wiring that runs
 over RCCL on the GPUs.  tests/test_multigpu.py runs the same thing with the HIP backend on 2 GPUs when they exist."""
 import os
 import socket
@@ -17,66 +17,14 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 
 REPO = Path(__file__).resolve().parents[1]
-NONE = np.uint64(0xFFFFFFFFFFFFFFFF)
+sys.path.insert(0, str(REPO / 'tests'))
+from search_ref import NumpySearchBackend  # noqa: E402  (the numpy statement of the kernels' contracts, shared with tests/test_search_gpu.py)
 
 
 def _free_port():
     with socket.socket() as s:
         s.bind(('127.0.0.1', 0))
         return s.getsockname()[1]
-
-
-class NumpySearchBackend:
-    """rf_l2_topk_keys / rf_topk_merge_keys / rf_demote_same_scene contracts in numpy (float64 distances rounded to fp32)."""
-
-    @staticmethod
-    def pack(emb_shard):
-        return emb_shard
-
-    @staticmethod
-    def _keys(q, emb, row_base, k2):
-        q, emb = q.numpy(), emb.numpy()
-        keys = np.full((q.shape[0], k2), NONE, dtype=np.uint64)
-        if emb.shape[0]:
-            d = ((q[:, None, :].astype(np.float64) - emb[None].astype(np.float64)) ** 2).sum(-1).astype(np.float32)
-            all_keys = (d.view(np.uint32).astype(np.uint64) << np.uint64(32)) | (np.arange(emb.shape[0], dtype=np.uint64) + np.uint64(row_base))[None]
-            all_keys.sort(axis=1)
-            m = min(k2, emb.shape[0])
-            keys[:, :m] = all_keys[:, :m]
-        return keys
-
-    @classmethod
-    def topk_keys(cls, q, packed, n, row_base, k2):
-        return torch.from_numpy(cls._keys(q, packed, row_base, k2).view(np.int64))
-
-    @staticmethod
-    def _unpack(keys):
-        none = keys == NONE
-        d = (keys >> np.uint64(32)).astype(np.uint32).view(np.float32)
-        i = (keys & np.uint64(0xFFFFFFFF)).astype(np.int64)
-        return torch.from_numpy(np.where(none, np.float32(np.inf), d)), torch.from_numpy(np.where(none, -1, i))
-
-    @classmethod
-    def topk(cls, q, packed, n, row_base, k2):
-        return cls._unpack(cls._keys(q, packed, row_base, k2))
-
-    @classmethod
-    def merge_keys(cls, key_parts):
-        k = key_parts.numpy().view(np.uint64)                           # [parts, nq, k2]
-        parts, nq, k2 = k.shape
-        flat = np.sort(k.transpose(1, 0, 2).reshape(nq, parts * k2), axis=1)[:, :k2]
-        return cls._unpack(flat)
-
-    @staticmethod
-    def demote(dist_, idx, meta, query_scene, K, query_keep):
-        sys.path.insert(0, str(REPO))
-        from oracle import refpath
-        idx_n, meta_n = idx.numpy(), meta.numpy()
-        rows = np.concatenate([np.where(idx_n[..., None] >= 0, meta_n[np.maximum(idx_n, 0)], np.array([-1, 0, 16, 0, 16, 0, 16])).astype(np.float32),
-                               dist_.numpy()[..., None]], axis=-1)
-        qs = query_scene.numpy() if query_scene is not None else np.full(idx_n.shape[0], -1)
-        out = refpath.demote_same_scene(rows, qs, K)
-        return torch.from_numpy(out[..., :7].astype(np.int32)), torch.from_numpy(out[..., 7].copy()), None
 
 
 def _problem(n_rows, world, nq_local):
