@@ -70,11 +70,22 @@ __device__ __forceinline__ float rf_attn_row_scores(const float* __restrict__ xf
     return smax;
 }
 
-__device__ __forceinline__ void rf_attn_row_weights(const float* __restrict__ xf_row, const float* __restrict__ pf_rows,
-                                                    const float* __restrict__ noise_row, int K, int f, int mode, float sharpness,
-                                                    float (&sc)[RF_MAX_K], float (&w)[RF_MAX_K], float& sw) {
-    const float smax = f == 32 ? rf_attn_row_scores<32>(xf_row, pf_rows, K, f, sc) : rf_attn_row_scores<0>(xf_row, pf_rows, K, f, sc);
+// What the backward (attention_backward.hip) needs beside the forward's results, from the SAME evaluation: y = the soft weights that carry the
+// gradient (softmax mode: y == w; Gumbel-hard: the y_soft of the straight-through form), smax = max_k scores, kstar = the FIRST index of the
+// maximal score (where max_pool1d / max(dim) send the switch's gradient) and hard = the slot Gumbel-hard chose (softmax mode: 0).  The forward
+// kernels call rf_attn_row_weights below, which drops them.
+__device__ __forceinline__ void rf_attn_row_weights_ex(const float* __restrict__ xf_row, const float* __restrict__ pf_rows,
+                                                       const float* __restrict__ noise_row, int K, int f, int mode, float sharpness,
+                                                       float (&sc)[RF_MAX_K], float (&w)[RF_MAX_K], float (&y)[RF_MAX_K], float& sw, float& smax,
+                                                       int& kstar, int& hard) {
+    smax = f == 32 ? rf_attn_row_scores<32>(xf_row, pf_rows, K, f, sc) : rf_attn_row_scores<0>(xf_row, pf_rows, K, f, sc);
     sw = rf_relu(smax);                                      // relu(max_k scores), model/attention.py:99
+    kstar = 0;
+    float best = -INFINITY;
+#pragma unroll
+    for (int k = 0; k < RF_MAX_K; ++k)
+        if (k < K && sc[k] > best) { best = sc[k]; kstar = k; }
+    hard = 0;
     if (mode == RF_ATTN_SOFTMAX) {
         // softmax(sharpness * scores): z = sharpness*s rounded first, then exp(z - zmax) / sum as torch does
         const float zmax = sharpness * smax;
@@ -85,7 +96,7 @@ __device__ __forceinline__ void rf_attn_row_weights(const float* __restrict__ xf
             den += w[k];
         }
 #pragma unroll
-        for (int k = 0; k < RF_MAX_K; ++k) w[k] = w[k] / den;
+        for (int k = 0; k < RF_MAX_K; ++k) { w[k] = w[k] / den; y[k] = w[k]; }
     } else {
         // gumbel_softmax(logits = 25*scores, tau = 1, hard = True): y_hard - y_soft + y_soft
         float lg[RF_MAX_K], lmax = -INFINITY;
@@ -106,6 +117,16 @@ __device__ __forceinline__ void rf_attn_row_weights(const float* __restrict__ xf
             const float ys = w[k] / den;
             const float yh = (k == arg) ? 1.f : 0.f;
             w[k] = (yh - ys) + ys;
+            y[k] = ys;
         }
+        hard = arg;
     }
+}
+
+__device__ __forceinline__ void rf_attn_row_weights(const float* __restrict__ xf_row, const float* __restrict__ pf_rows,
+                                                    const float* __restrict__ noise_row, int K, int f, int mode, float sharpness,
+                                                    float (&sc)[RF_MAX_K], float (&w)[RF_MAX_K], float& sw) {
+    float y[RF_MAX_K], smax;
+    int kstar, hard;
+    rf_attn_row_weights_ex(xf_row, pf_rows, noise_row, K, f, mode, sharpness, sc, w, y, sw, smax, kstar, hard);
 }

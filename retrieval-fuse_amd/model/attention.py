@@ -1,7 +1,9 @@
 """Patch attention -- MI355X-native stand-ins for the reference's model/attention.py (same names, constructor
 arguments, ``state_dict`` keys incl. the unused-but-serialised sig_scale / sig_shift).  The no-grad route below is the
-hot path; with grad enabled and inputs that require it the modules take rfuse/autograd.py (HIP kernels for the Linear layers,
-plain differentiable torch ops for the per-row weights and the blend: the N4 training slice).
+hot path; with grad enabled and inputs that require it the modules take rfuse/autograd.py (the N4 training slice): the same row-route kernels
+behind torch.autograd.Functions -- Linear for the encoders, AttnFuse (rf_attn_fuse / rf_attn_fuse_backward) for everything after them,
+Unfold3d / Fold3d / GatherRetrieved for the index maps.  No torch formula is left in this stage; the switch's gradient goes to the first maximal
+score, as the reference's MaxPool1d(K) sends it.
 
   AttentionFeatureEncoder  = 4 x rf_linear (fp32 MFMA GEMM, LeakyReLU(0.01) fused)          reference :29-46
   AttentionBlock.forward   = theta/phi encoders + rf_attn_fuse                               reference :84-113
@@ -137,25 +139,20 @@ class AttentionBlock(nn.Module):
         return ops.l2_normalize_rows_(x_feat), ops.l2_normalize_rows_(p_feat)
 
     def _forward_autograd(self, x, p, gumbel_noise):
-        """Grad mode (training slice): the two feature encoders run rf_linear behind rfuse.autograd.Linear (the
-        GEMMs are 99 % of this block's work); the per-row rest -- normalise, K scores, switch, softmax / straight-through
-        Gumbel-hard, mix, blend -- is a few elementwise torch ops that autograd differentiates."""
-        b, k = p.shape[0], p.shape[1]
-        xf = nn.functional.normalize(self.theta(x), dim=1)
-        pf = nn.functional.normalize(self.phi(p.reshape((b * k,) + tuple(p.shape[2:]))), dim=1).reshape(b, k, -1)
-        scores = (xf.unsqueeze(1) * pf).sum(dim=2)                                   # [b, K]
-        switch = scores.amax(dim=1, keepdim=True).clamp_min(0.0)
+        """Grad mode (training slice): the two feature encoders run rf_linear behind rfuse.autograd.Linear, their raw
+        (un-normalised) outputs go to rfuse.autograd.AttnFuse: rf_attn_fuse forward, one rf_attn_fuse_backward launch backward."""
+        from rfuse import autograd as rf_autograd
+        b, k, c, e = p.shape[0], p.shape[1], p.shape[2], p.shape[3]
+        x, p = x.contiguous(), p.contiguous()
+        # phi before theta: autograd runs the later-built branch first, so theta's (K times smaller) backward is over and its saved activations,
+        # the unfolded x rows among them, are released before phi's Linear backward on K times the rows -- where the stage's peak of memory lies
+        p_feat = self.phi(p.reshape(b * k, c, e, e, e))
+        x_feat = self.theta(x)
         if self.retrieval_mode:
             if gumbel_noise is None:
                 gumbel_noise = self.sample_gumbel(b, k, x.device)
-            soft = torch.softmax(scores * 25.0 + gumbel_noise, dim=1)
-            hard = torch.zeros_like(soft).scatter_(1, soft.argmax(dim=1, keepdim=True), 1.0)
-            weights = hard - soft.detach() + soft                                    # straight-through estimator of gumbel_softmax(hard=True)
-        else:
-            weights = torch.softmax(scores * float((self.cf_feat * self.patch_extent ** 3) * 4), dim=1)
-        mixed = (weights.unsqueeze(2) * p.reshape(b, k, -1)).sum(dim=1)
-        flat = x.reshape(b, -1)
-        return (flat * (1.0 - switch) + mixed * switch).reshape(x.shape)
+            return rf_autograd.AttnFuse.apply(x, p, x_feat, p_feat, gumbel_noise.detach().contiguous(), ops.ATTN_GUMBEL_HARD, 25.0)
+        return rf_autograd.AttnFuse.apply(x, p, x_feat, p_feat, None, ops.ATTN_SOFTMAX, float((self.cf_feat * e * e * e) * 4))
 
     def forward(self, x, p, gumbel_noise=None, debug=None):
         """x: [B,C,E,E,E]; p: [B,K,C,E,E,E] -> [B,C,E,E,E]; reference :84-113."""
@@ -232,24 +229,20 @@ class PatchedAttentionBlock(nn.Module):
         occupancy_flat = occupancy_.reshape((x_predicted_feat_.shape[0], -1)).ne(0).any(dim=1)
         return x_feat_flat, p_feat_flat, occupancy_flat
 
-    def _forward_autograd(self, x_predicted, x_retrieved, gumbel_noise):
-        """grad mode: unfold / regroup / fold as differentiable views (no kernels), AttentionBlock._forward_autograd in between"""
-        b, c, s = x_predicted.shape[0], x_predicted.shape[1], x_predicted.shape[-1]
-        e, k = self.patch_extent, self.num_nearest_neighbors
-        r = s // e
-
-        def rows(v):                                                    # [n, c, s,s,s] -> [n, r,r,r, c, e,e,e]
-            return v.reshape(v.shape[0], c, r, e, r, e, r, e).permute(0, 2, 4, 6, 1, 3, 5, 7)
-        x_rows = rows(x_predicted).reshape(-1, c, e, e, e)
-        p_rows = rows(x_retrieved).reshape(b, k, r, r, r, c, e, e, e).permute(0, 2, 3, 4, 1, 5, 6, 7, 8).reshape(-1, k, c, e, e, e)
-        out = self.attention_blocks_layer(x_rows, p_rows, gumbel_noise)
-        return out.reshape(b, r, r, r, c, e, e, e).permute(0, 4, 1, 5, 2, 6, 3, 7).reshape(b, c, s, s, s)
+    def _forward_autograd(self, x_predicted, retrieved, layout, patch_edge, gumbel_noise):
+        """grad mode: the row route's own kernels behind rfuse.autograd (Unfold3d -> GatherRetrieved -> AttentionBlock -> Fold3d); ``layout`` 0:
+        ``retrieved`` are folded volumes, 1: the retrieval backbone's patch-major features with patch edge ``patch_edge``"""
+        from rfuse import autograd as rf_autograd
+        b, s = x_predicted.shape[0], x_predicted.shape[-1]
+        x_rows = self.unfold_3d(x_predicted)
+        p_rows = rf_autograd.GatherRetrieved.apply(retrieved, layout, b, self.num_nearest_neighbors, self.nf, s, self.patch_extent, patch_edge)
+        return self.fold_3d(self.attention_blocks_layer(x_rows, p_rows, gumbel_noise))
 
     def forward(self, x_predicted, x_retrieved, gumbel_noise=None, debug=None):
         """x_predicted [B,F,S,S,S]; x_retrieved [B*K,F,S,S,S] (folded volumes) -> [B,F,S,S,S]."""
         b, s = x_predicted.shape[0], x_predicted.shape[-1]
         if ops.needs_grad(x_predicted, x_retrieved, self.attention_blocks_layer.theta.encoder[0].weight):
-            return self._forward_autograd(x_predicted, x_retrieved, gumbel_noise)
+            return self._forward_autograd(x_predicted, x_retrieved, 0, 0, gumbel_noise)
         if self.attention_blocks_layer.volume_route_ok():
             return self.attention_blocks_layer.forward_volumes(x_predicted, x_retrieved, s, gumbel_noise, debug)
         x_rows = self.unfold_3d(x_predicted)
@@ -263,9 +256,7 @@ class PatchedAttentionBlock(nn.Module):
         is never materialised."""
         b, s = x_predicted.shape[0], x_predicted.shape[-1]
         if ops.needs_grad(x_predicted, retrieved_patch_features, self.attention_blocks_layer.theta.encoder[0].weight):
-            q, c = s // patch_edge, x_predicted.shape[1]               # fold the patch-major features (Fold3D semantics) as a view
-            vols = retrieved_patch_features.reshape(-1, q, q, q, c, patch_edge, patch_edge, patch_edge).permute(0, 4, 1, 5, 2, 6, 3, 7).reshape(-1, c, s, s, s)
-            return self._forward_autograd(x_predicted, vols, gumbel_noise)
+            return self._forward_autograd(x_predicted, retrieved_patch_features, 1, patch_edge, gumbel_noise)
         if self.attention_blocks_layer.volume_route_ok():
             return self.attention_blocks_layer.forward_volumes(x_predicted, retrieved_patch_features, patch_edge, gumbel_noise)
         x_rows = self.unfold_3d(x_predicted)
@@ -285,9 +276,9 @@ class Fold3D(nn.Module):
         self.patch_extent = patch_extent
 
     def forward(self, x):
-        if ops.needs_grad(x):                                           # grad mode: the same index map as a differentiable view
-            r, e, c = self.num_patch_x, self.patch_extent, self.nf
-            return x.reshape(-1, r, r, r, c, e, e, e).permute(0, 4, 1, 5, 2, 6, 3, 7).reshape(-1, c, r * e, r * e, r * e)
+        if ops.needs_grad(x):                                           # grad mode: the same kernel, rf_unfold3d as its backward
+            from rfuse import autograd as rf_autograd
+            return rf_autograd.Fold3d.apply(x, self.num_patch_x, self.patch_extent, self.nf)
         return ops.fold3d(x.contiguous(), self.num_patch_x, self.patch_extent, self.nf)
 
 
@@ -300,7 +291,7 @@ class Unfold3D(nn.Module):
         self.nf = nf
 
     def forward(self, x):
-        if ops.needs_grad(x):
-            e, c, r = self.patch_extent, x.shape[1], x.shape[2] // self.patch_extent
-            return x.reshape(x.shape[0], c, r, e, r, e, r, e).permute(0, 2, 4, 6, 1, 3, 5, 7).reshape(-1, c, e, e, e)
+        if ops.needs_grad(x):                                           # grad mode: the same kernel, rf_fold3d as its backward
+            from rfuse import autograd as rf_autograd
+            return rf_autograd.Unfold3d.apply(x, self.patch_extent)
         return ops.unfold3d(x.contiguous(), self.patch_extent)

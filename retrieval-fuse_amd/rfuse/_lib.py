@@ -1,5 +1,6 @@
 """ctypes binding of librfuse_hip.so (the C ABI declared in include/rfuse.h, the evaluation ABI of include/rfuse_eval.h, the training-loss ABI
-of include/rfuse_train.h, the contrastive-loss ABI of include/rfuse_contrastive.h and the pairwise-occupancy ABI of include/rfuse_pairs.h).
+of include/rfuse_train.h, the contrastive-loss ABI of include/rfuse_contrastive.h, the pairwise-occupancy ABI of include/rfuse_pairs.h and the
+attention-backward ABI of include/rfuse_attn_train.h).
 
 The argument and return types are read from the header itself at import (``parse_header``): there is no second copy of the ABI to keep
 in step.  There is NO fallback: if the library is missing a RuntimeError is raised, and every entry point that returns a status
@@ -9,8 +10,8 @@ first so that the HIP runtime the library binds to is the one PyTorch-ROCm alrea
 ``load()`` binds include/rfuse.h (``SIGNATURES``; the profiling wrapper brackets these); ``load_eval()`` binds include/rfuse_eval.h
 (``EVAL_SIGNATURES``: the mesh metrics, rfuse/mesh_metrics.py) and ``load_train()`` include/rfuse_train.h (``TRAIN_SIGNATURES``: the shape loss,
 rfuse/losses.py) and ``load_contrastive()`` include/rfuse_contrastive.h (``CONTRASTIVE_SIGNATURES``: NT-Xent and the sliced attention contrastive
-loss, rfuse/losses.py) and ``load_pairs()`` include/rfuse_pairs.h (``PAIRS_SIGNATURES``: the retrieval trainer's IoU matrix, rfuse/losses.py), all from
-the same shared object, under the same status rule.
+loss, rfuse/losses.py) and ``load_pairs()`` include/rfuse_pairs.h (``PAIRS_SIGNATURES``: the retrieval trainer's IoU matrix, rfuse/losses.py) and ``load_attn_train()`` include/rfuse_attn_train.h
+(``ATTN_TRAIN_SIGNATURES``: the backward of the patch attention's row route, rfuse/ops.py), all from the same shared object, under the same status rule.
 """
 import ctypes
 import os
@@ -26,6 +27,7 @@ EVAL_HEADER_PATH = _HERE.parents[1] / 'include' / 'rfuse_eval.h'
 TRAIN_HEADER_PATH = _HERE.parents[1] / 'include' / 'rfuse_train.h'
 CONTRASTIVE_HEADER_PATH = _HERE.parents[1] / 'include' / 'rfuse_contrastive.h'
 PAIRS_HEADER_PATH = _HERE.parents[1] / 'include' / 'rfuse_pairs.h'
+ATTN_TRAIN_HEADER_PATH = _HERE.parents[1] / 'include' / 'rfuse_attn_train.h'
 
 # every scalar type include/rfuse.h uses; any pointer is a c_void_p, and `const char*` as a return type a c_char_p
 _SCALARS = {'int': ctypes.c_int, 'float': ctypes.c_float, 'size_t': ctypes.c_size_t, 'int64_t': ctypes.c_int64, 'long long': ctypes.c_int64}
@@ -77,6 +79,7 @@ EVAL_SIGNATURES = parse_header(EVAL_HEADER_PATH.read_text())
 TRAIN_SIGNATURES = parse_header(TRAIN_HEADER_PATH.read_text())
 CONTRASTIVE_SIGNATURES = parse_header(CONTRASTIVE_HEADER_PATH.read_text())
 PAIRS_SIGNATURES = parse_header(PAIRS_HEADER_PATH.read_text())
+ATTN_TRAIN_SIGNATURES = parse_header(ATTN_TRAIN_HEADER_PATH.read_text())
 
 
 def is_status(name, table=None):
@@ -96,6 +99,7 @@ _eval = None
 _train = None
 _contrastive = None
 _pairs = None
+_attn_train = None
 
 
 class _Library:
@@ -181,6 +185,14 @@ def load_pairs():
     if _pairs is None:
         _pairs = _Library(load()._cdll, PAIRS_SIGNATURES)
     return _pairs
+
+
+def load_attn_train():
+    """The entry points of include/rfuse_attn_train.h, bound like ``load_eval()``'s."""
+    global _attn_train
+    if _attn_train is None:
+        _attn_train = _Library(load()._cdll, ATTN_TRAIN_SIGNATURES)
+    return _attn_train
 
 
 def check(rc, what):

@@ -23,9 +23,15 @@ retrieval_backbone / attention parameters, :295-306 phase hand-over).  Built her
                 operands throughout, so NT-Xent's small gradients (1e-3 ... 1e-7) need no rescaling.
                 The MLP patch encoders (Patch04 / Patch05 / Patch04V2) and every encoder's final_layer run through Linear below.
 
+  AttnFuse     the patch attention after its encoders (reference model/attention.py:92-110): normalise, K scores, switch, softmax | Gumbel-hard, mix, blend
+      forward   rf_attn_fuse (the inference kernel; only its inputs are saved)
+      backward  rf_attn_fuse_backward: one launch for dx, dp and the gradients of the RAW encoder outputs; the row's decisions are recomputed with the
+                forward's code; the switch's gradient goes to the first maximal score like MaxPool1d(K); Gumbel-hard as torch's straight-through form
+  Unfold3d / Fold3d / GatherRetrieved   rf_unfold3d <-> rf_fold3d, rf_attn_gather_retrieved -> rf_attn_scatter_retrieved (pure index maps, same bits as
+                the permuted views they replace)
+
 torch does the bookkeeping and the light per-row work: transposes / flips of weights, the activation mask of Linear, sums over the batch of
-per-sample float64 pieces, the 16 -> 1 pointwise conv + tanh of the final decoder, fold / unfold as views, and the patch attention's per-row
-normalise / scores / softmax or straight-through Gumbel-hard / blend (model/attention.py:_forward_autograd) -- together < 1 % of the FLOPs.  With
+per-sample float64 pieces, the 16 -> 1 pointwise conv + tanh of the final decoder and the Gumbel noise draw -- together < 1 % of the FLOPs.  With
 that the whole training graph of the reference (trainer/train_refinement.py:108-116 forward_full, all four networks trainable = phase 3) runs
 through the drop-in modules in grad mode; loss and every parameter gradient are checked against float64 autograd of the oracle in
 tests/test_autograd_gpu.py.  Not built: backward of the pre-split pair routes and the fused attention MLP (grad mode takes the plain routes), the
@@ -217,6 +223,73 @@ class Linear(torch.autograd.Function):
             dw = ops.linear_wgrad(dpre, x)
             db = dpre.double().sum(0).float() if ctx.has_bias else None
         return dx, dw, db, None, None
+
+
+class AttnFuse(torch.autograd.Function):
+    """rf_attn_fuse forward, rf_attn_fuse_backward backward: x [b,c,e,e,e]-like, p [b,K,...], xf [b,f] / pf [b*K,f] the RAW encoder outputs, noise [b,K]
+    or None.  Only the inputs are saved: the backward kernel recomputes the row's scores, switch and weights with the forward's code."""
+
+    @staticmethod
+    def forward(ctx, x, p, xf, pf, noise, mode, sharpness):
+        x, p, xf, pf = x.contiguous(), p.contiguous(), xf.contiguous(), pf.contiguous()
+        noise = noise.contiguous() if noise is not None else None
+        ctx.save_for_backward(x, p, xf, pf, noise)
+        ctx.mode, ctx.sharpness = mode, sharpness
+        with torch.no_grad():
+            return ops.attn_fuse(x, p, xf, pf, noise, mode, sharpness)
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, p, xf, pf, noise = ctx.saved_tensors
+        with torch.no_grad():
+            dx, dp, dxf, dpf = ops.attn_fuse_backward(x, p, xf, pf, noise, dout.contiguous(), ctx.mode, ctx.sharpness, ctx.needs_input_grad[:4])
+        return dx, dp, dxf, dpf, None, None, None
+
+
+class Unfold3d(torch.autograd.Function):
+    """rf_unfold3d forward, rf_fold3d backward (each is the other's exact inverse index map)"""
+
+    @staticmethod
+    def forward(ctx, x, e):
+        ctx.r, ctx.e, ctx.c = x.shape[2] // e, e, x.shape[1]
+        with torch.no_grad():
+            return ops.unfold3d(x.contiguous(), e)
+
+    @staticmethod
+    def backward(ctx, drows):
+        with torch.no_grad():
+            return ops.fold3d(drows.contiguous(), ctx.r, ctx.e, ctx.c), None
+
+
+class Fold3d(torch.autograd.Function):
+    """rf_fold3d forward, rf_unfold3d backward"""
+
+    @staticmethod
+    def forward(ctx, rows, r, e, c):
+        ctx.e = e
+        with torch.no_grad():
+            return ops.fold3d(rows.contiguous(), r, e, c)
+
+    @staticmethod
+    def backward(ctx, dx):
+        with torch.no_grad():
+            return ops.unfold3d(dx.contiguous(), ctx.e), None, None, None
+
+
+class GatherRetrieved(torch.autograd.Function):
+    """rf_attn_gather_retrieved forward (layout 0: folded volumes, 1: the retrieval backbone's patch-major output), rf_attn_scatter_retrieved backward"""
+
+    @staticmethod
+    def forward(ctx, src, layout, b, k, c, s, e, t):
+        ctx.args, ctx.shape = (layout, b, k, c, s, e, t), src.shape
+        with torch.no_grad():
+            return ops.attn_gather_retrieved(src.contiguous(), layout, b, k, c, s, e, t)
+
+    @staticmethod
+    def backward(ctx, dp_rows):
+        with torch.no_grad():
+            dsrc = ops.attn_scatter_retrieved(dp_rows.contiguous(), *ctx.args)
+        return dsrc.reshape(ctx.shape), None, None, None, None, None, None, None
 
 
 class ConvValidLeaky(torch.autograd.Function):

@@ -67,7 +67,8 @@ def _no_grad_only(*tensors):
     if needs_grad(*tensors):
         raise NotImplementedError(
             'this rfuse op implements inference only; call under torch.no_grad().  Backward exists for the SingleConv layers, '
-            'the attention feature encoders and the patch encoders\' forward (rfuse/autograd.py, SURVEY.md section 8f row N4), not for this op')
+            'the attention feature encoders, the row route of the patch attention (attn_fuse, unfold3d / fold3d, attn_gather_retrieved) and the patch '
+            'encoders\' forward (rfuse/autograd.py, SURVEY.md section 8f row N4), not for this op')
 
 
 _ws_cache = {}
@@ -985,6 +986,35 @@ def attn_fuse(x, p, xf, pf, noise, mode, sharpness, debug=False):
     _lib.load().rf_attn_fuse(_p(x), _p(p), _p(xf), _p(pf), _p(noise), b, k, d, f, mode, sharpness, _p(out), _p(sc), _p(wt),
                              _stream())
     return (out, sc, wt) if debug else out
+
+
+def attn_fuse_backward(x, p, xf, pf, noise, dout, mode, sharpness, need=(True, True, True, True)):
+    """Gradient of attn_fuse for its inputs (same tensors, same layouts) and ``dout`` shaped like x -> (dx, dp, dxf, dpf), each shaped like its
+    input; ``need[i]`` False: that gradient is neither computed nor written and comes back as None.  One launch (rf_attn_fuse_backward)."""
+    _req(x, 'x'), _req(p, 'p'), _req(xf, 'xf'), _req(pf, 'pf'), _req(dout, 'dout')
+    if noise is not None:
+        _req(noise, 'noise')
+    if dout.shape != x.shape:
+        raise ValueError('attn_fuse_backward: dout %s is not shaped like x %s' % (tuple(dout.shape), tuple(x.shape)))
+    b, k, d, f = x.shape[0], p.shape[1], x[0].numel(), xf.shape[1]
+    if p.numel() != b * k * d or xf.numel() != b * f or pf.numel() != b * k * f or (noise is not None and noise.numel() != b * k):
+        raise ValueError('attn_fuse_backward: x %s, p %s, xf %s, pf %s do not describe %d rows of K=%d' % (tuple(x.shape), tuple(p.shape), tuple(xf.shape), tuple(pf.shape), b, k))
+    outs = [torch.empty_like(t) if n else None for t, n in zip((x, p, xf, pf), need)]
+    _lib.load_attn_train().rf_attn_fuse_backward(_p(x), _p(p), _p(xf), _p(pf), _p(noise), _p(dout), b, k, d, f, mode, sharpness,
+                                      _p(outs[0]), _p(outs[1]), _p(outs[2]), _p(outs[3]), _stream())
+    return tuple(outs)
+
+
+def attn_scatter_retrieved(dp_rows, layout, b, k, c, s, e, t=0):
+    """Backward of attn_gather_retrieved: dp_rows [(b*r^3), K, c, e,e,e] -> the gradient in the layout of its src (0: [b*K, c, s,s,s]; 1: patch-major
+    [(b*K*q^3), c, t,t,t]).  The exact inverse index map: every element written once."""
+    _req(dp_rows, 'dp_rows')
+    if dp_rows.numel() != b * k * c * s * s * s:
+        raise ValueError('attn_scatter_retrieved: %d values do not tile [%d*%d, %d, %d^3]' % (dp_rows.numel(), b, k, c, s))
+    shape = (b * k, c, s, s, s) if layout == 0 or t <= 0 else (b * k * (s // t) ** 3, c, t, t, t)
+    dsrc = torch.empty(shape, dtype=torch.float32, device=dp_rows.device)
+    _lib.load_attn_train().rf_attn_scatter_retrieved(_p(dp_rows), layout, b, k, c, s, e, t, _p(dsrc), _stream())
+    return dsrc
 
 
 USE_FUSED_ATTN_MLP = True       # False: per-layer rf_linear + the row-domain attention kernels (kept for cross-checks)
