@@ -16,7 +16,9 @@ err_ref as the generator printed it (loss: relative; gradients: max-abs over max
     ragged    loss 6.7e-8   grad fpred 1.7e-7   ftgt 1.7e-7
     empty     loss 0        grad       0
     trainer   loss 7.6e-8   grad fpred 2.8e-7   ftgt 2.7e-7
-Counts, the selection and exact-zero patterns are compared exactly."""
+Counts, the selection and exact-zero patterns are compared exactly.
+The fixture stops at 64 features and 512 pairs in two occupied slices: widths above 64 (several feature chunks), the trainer's own geometry and one large
+group are in tests/test_loss_sweep_gpu.py, on generated cases against the float64 restatement."""
 import contextlib
 import io
 
