@@ -247,17 +247,52 @@ class Encoder(nn.Module):
         self.basic_module = basic_module(in_channels, out_channels, encoder=True, kernel_size=conv_kernel_size,
                                          order=conv_layer_order, num_groups=num_groups)
 
-    def forward(self, x, prepooled=None, pool=None, next_block=None):
+    def level_route(self, n, c, edge, grad=False, skip=None):
+        """the name rfuse.routes.level gives this level on an unpooled input [n, c, edge^3] ('plain' for a level without pooling or whose basic module is no
+        DoubleConv); ``skip``: see routes.level"""
+        bm = self.basic_module
+        if not self.apply_pooling or not isinstance(bm, DoubleConv) or bm.SingleConv1.conv.in_channels != c:
+            return 'plain'
+        c1, c2 = bm.SingleConv1, bm.SingleConv2
+        grad = grad or (torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()))
+        return routes.level(n, c, edge, c1.conv.out_channels, c2.conv.out_channels, ops._gn_groups(c, c1.groupnorm.num_groups),
+                            ops._gn_groups(c1.conv.out_channels, c2.groupnorm.num_groups), grad, c1.range_ok(edge // 2), c2.range_ok(edge // 2), skip=skip)
+
+    def forward(self, x, prepooled=None, pool=None, next_block=None, consumer=None):
         """``prepooled``: MaxPool3d(2)(x) when the producer already emitted it (fused epilogue; an ops.PreSplit when it was handed over pre-split);
-        ``pool``: see SingleConv.forward; ``next_block``: see DoubleConv.forward."""
+        ``pool``: see SingleConv.forward; ``next_block``: see DoubleConv.forward; ``consumer``: (skip tensor, GroupNormParams) of the decoder stage that
+        will read this level's output upsampled beside that skip tensor, when the caller knows it -- a level that runs as one launch writes that
+        GroupNorm's table as well (DESIGN 10.7: the LATER producer of a straddling GroupNorm has both halves' statistics)."""
         if self.apply_pooling:
             if prepooled is not None:
                 x = prepooled
             elif ops.needs_grad(x):
                 x = torch.nn.functional.max_pool3d(x, 2)            # grad mode: torch's max-pool carries the backward
             else:
+                if pool is None and x.dim() == 5:
+                    done = self._whole_level(x, consumer)
+                    if done is not None:
+                        return done
                 x = ops.maxpool2(x)
         return self.basic_module(x, pool=pool, next_block=next_block)
+
+    def _whole_level(self, x, consumer):
+        """the level as one launch where routes.level names that form, else None"""
+        n, c, edge = x.shape[0], x.shape[1], x.shape[2]
+        skip = gn_dec = None
+        if consumer is not None and consumer[0] is not None:
+            st = ops._fresh_stats(consumer[0])
+            if st is not None:
+                skip, gn_dec = consumer
+        cout = self.basic_module.SingleConv2.conv.out_channels if isinstance(self.basic_module, DoubleConv) else 0
+        plan = None if skip is None else (skip.shape[1], st[1], ops._gn_groups(skip.shape[1] + cout, gn_dec.num_groups))
+        if self.level_route(n, c, edge, skip=plan) != 'e2_level':
+            return None
+        c1, c2 = self.basic_module.SingleConv1, self.basic_module.SingleConv2
+        g1, g2 = c1.groupnorm, c2.groupnorm
+        return ops.conv3d_e2_level(x, (g1.weight, g1.bias, g1.num_groups, g1.eps), c1.conv.packed_e2_split(2), c1.conv.out_channels,
+                                   (g2.weight, g2.bias, g2.num_groups, g2.eps), c2.conv.packed_e2_split(2), cout, skip=skip,
+                                   gn_dec=None if skip is None else (gn_dec.weight, gn_dec.bias, gn_dec.num_groups, gn_dec.eps))
 
 
 class Decoder(nn.Module):
@@ -328,11 +363,21 @@ class UNet3D(nn.Module):
             # a skip only for levels n_enc-1-n_dec .. n_enc-2 (model/unet.py:500-507: the list is cut and zip() truncates, so
             # with remove_n_final_layers the finest levels are never joined).  Unread outputs are not even written.
             if i == n_enc - 1:
-                x, pooled = encoder(x, prepooled=pooled), None
+                # the decoder stage that reads this output beside the previous level's: its GroupNorm's table can come out of this level's launch
+                consumer = (feats[0], self.decoders[0].basic_module.SingleConv1.groupnorm) if n_dec > 0 and feats and isinstance(self.decoders[0], Decoder) \
+                    and not isinstance(self.decoders[0], DecoderNoJoining) else None
+                x, pooled = encoder(x, prepooled=pooled, consumer=consumer), None
             else:
                 is_skip = i >= n_enc - 1 - n_dec
                 nxt = self.encoders[i + 1].basic_module
-                x, pooled = encoder(x, prepooled=pooled, pool='also' if is_skip else 'only', next_block=nxt if isinstance(nxt, DoubleConv) else None)
+                cout = encoder.basic_module.SingleConv2.conv.out_channels
+                src = pooled if pooled is not None else x            # what this level's convs read: its output has that batch and edge
+                n, edge = (src.n, src.edge) if isinstance(src, ops.PreSplit) else (src.shape[0], src.shape[2])
+                if i == n_enc - 2 and is_skip and self.encoders[i + 1].level_route(n, cout, edge, ops.needs_grad(x)) == 'e2_level':
+                    # the last level pools for itself, inside its one launch: this one writes its output only
+                    x, pooled = encoder(x, prepooled=pooled, next_block=nxt if isinstance(nxt, DoubleConv) else None), None
+                else:
+                    x, pooled = encoder(x, prepooled=pooled, pool='also' if is_skip else 'only', next_block=nxt if isinstance(nxt, DoubleConv) else None)
             feats.insert(0, x)
         feats = feats[1:]                                            # model/unet.py:500-504
         if after_encoders is not None:

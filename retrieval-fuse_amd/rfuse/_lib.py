@@ -1,6 +1,6 @@
 """ctypes binding of librfuse_hip.so (the C ABI declared in include/rfuse.h, the evaluation ABI of include/rfuse_eval.h, the training-loss ABI
-of include/rfuse_train.h, the contrastive-loss ABI of include/rfuse_contrastive.h, the pairwise-occupancy ABI of include/rfuse_pairs.h and the
-attention-backward ABI of include/rfuse_attn_train.h).
+of include/rfuse_train.h, the contrastive-loss ABI of include/rfuse_contrastive.h, the pairwise-occupancy ABI of include/rfuse_pairs.h, the
+attention-backward ABI of include/rfuse_attn_train.h and the level ABI of include/rfuse_level.h).
 
 The argument and return types are read from the header itself at import (``parse_header``): there is no second copy of the ABI to keep
 in step.  There is NO fallback: if the library is missing a RuntimeError is raised, and every entry point that returns a status
@@ -11,7 +11,8 @@ first so that the HIP runtime the library binds to is the one PyTorch-ROCm alrea
 (``EVAL_SIGNATURES``: the mesh metrics, rfuse/mesh_metrics.py) and ``load_train()`` include/rfuse_train.h (``TRAIN_SIGNATURES``: the shape loss,
 rfuse/losses.py) and ``load_contrastive()`` include/rfuse_contrastive.h (``CONTRASTIVE_SIGNATURES``: NT-Xent and the sliced attention contrastive
 loss, rfuse/losses.py) and ``load_pairs()`` include/rfuse_pairs.h (``PAIRS_SIGNATURES``: the retrieval trainer's IoU matrix, rfuse/losses.py) and ``load_attn_train()`` include/rfuse_attn_train.h
-(``ATTN_TRAIN_SIGNATURES``: the backward of the patch attention's row route, rfuse/ops.py), all from the same shared object, under the same status rule.
+(``ATTN_TRAIN_SIGNATURES``: the backward of the patch attention's row route, rfuse/ops.py) and ``load_level()`` include/rfuse_level.h (``LEVEL_SIGNATURES``:
+a whole encoder level in one launch, rfuse/ops.py), all from the same shared object, under the same status rule.
 """
 import ctypes
 import os
@@ -28,6 +29,7 @@ TRAIN_HEADER_PATH = _HERE.parents[1] / 'include' / 'rfuse_train.h'
 CONTRASTIVE_HEADER_PATH = _HERE.parents[1] / 'include' / 'rfuse_contrastive.h'
 PAIRS_HEADER_PATH = _HERE.parents[1] / 'include' / 'rfuse_pairs.h'
 ATTN_TRAIN_HEADER_PATH = _HERE.parents[1] / 'include' / 'rfuse_attn_train.h'
+LEVEL_HEADER_PATH = _HERE.parents[1] / 'include' / 'rfuse_level.h'
 
 # every scalar type include/rfuse.h uses; any pointer is a c_void_p, and `const char*` as a return type a c_char_p
 _SCALARS = {'int': ctypes.c_int, 'float': ctypes.c_float, 'size_t': ctypes.c_size_t, 'int64_t': ctypes.c_int64, 'long long': ctypes.c_int64}
@@ -80,6 +82,7 @@ TRAIN_SIGNATURES = parse_header(TRAIN_HEADER_PATH.read_text())
 CONTRASTIVE_SIGNATURES = parse_header(CONTRASTIVE_HEADER_PATH.read_text())
 PAIRS_SIGNATURES = parse_header(PAIRS_HEADER_PATH.read_text())
 ATTN_TRAIN_SIGNATURES = parse_header(ATTN_TRAIN_HEADER_PATH.read_text())
+LEVEL_SIGNATURES = parse_header(LEVEL_HEADER_PATH.read_text())
 
 
 def is_status(name, table=None):
@@ -100,6 +103,7 @@ _train = None
 _contrastive = None
 _pairs = None
 _attn_train = None
+_level = None
 
 
 class _Library:
@@ -193,6 +197,14 @@ def load_attn_train():
     if _attn_train is None:
         _attn_train = _Library(load()._cdll, ATTN_TRAIN_SIGNATURES)
     return _attn_train
+
+
+def load_level():
+    """The entry points of include/rfuse_level.h, bound like ``load_eval()``'s (its ``start_profile`` brackets them: their launch log)."""
+    global _level
+    if _level is None:
+        _level = _Library(load()._cdll, LEVEL_SIGNATURES)
+    return _level
 
 
 def check(rc, what):

@@ -183,6 +183,9 @@ def gn_affine(src0, src1, gamma, beta, groups, eps=1e-5):
             _req(t, nm)
     _req(gamma.detach(), 'gamma'), _req(beta.detach(), 'beta')
     n, c0, c1, edge = _src_dims(src0, src1)
+    ready = _ready_affine(src0, src1, gamma, beta, groups, eps)
+    if ready is not None:                                    # the launch that wrote src1 had both halves' statistics: it wrote the table too
+        return ready
     c = c0 + c1
     if c < groups:
         groups = 1                                           # model/unet.py:62-63
@@ -420,6 +423,56 @@ def conv3d_e2_split_gn_relu(src, aff, w_e2_packed, cout):
     out = torch.empty((n, cout, edge, edge, edge), dtype=torch.float32, device=dev)
     _lib.load().rf_conv3d_e2_split_k3_gn_relu(_p(src), cin, n, edge, _p(aff), _p(w_e2_packed), cout, _p(out), _p(_attach_stats(out, 1)), _stream())
     return out
+
+
+USE_E2_LEVEL = True             # False: an encoder level on 2^3 volumes runs its six launches (max-pool, GroupNorm, conv, GroupNorm, conv, the decoder's GroupNorm)
+
+
+def _gn_groups(c, groups):
+    return 1 if c < groups else groups                       # model/unet.py:62-63
+
+
+def conv3d_e2_level(x, gn1, w1_e2_packed, cmid, gn2, w2_e2_packed, cout, skip=None, gn_dec=None):
+    """ReLU(conv3(GN2(ReLU(conv3(GN1(MaxPool3d(2)(x))))))) of x [n, c, 4,4,4] in one launch (csrc/conv3d_e2_level.hip), bit for bit what maxpool2, gn_affine,
+    conv3d_e2_split_gn_relu, gn_affine, conv3d_e2_split_gn_relu give; gn1 / gn2 = (gamma, beta, groups, eps); the weights as pack_conv3_e2_split_weight(w, 2)
+    images.  The output's statistics ride along.  ``skip`` [n, c_skip, 4,4,4] with producer statistics and ``gn_dec``: the launch also writes the triples of
+    GroupNorm(cat(skip, up2(out))) and leaves them on the output, where gn_affine(skip, out, *gn_dec) finds them (computed in this call from these
+    parameters; nothing outlives the output tensor)."""
+    _req(x, 'x')
+    n, c, _, edge = _src_dims(x, None)
+    if edge != 4:
+        raise ValueError('conv3d_e2_level: expected 4^3 volumes, got %s' % (tuple(x.shape),))
+    for g in (gn1, gn2) + ((gn_dec,) if skip is not None else ()):
+        _req(g[0].detach(), 'gamma'), _req(g[1].detach(), 'beta')
+    lib = _lib.load_level()
+    out = torch.empty((n, cout, 2, 2, 2), dtype=torch.float32, device=x.device)
+    stats = _attach_stats(out, 1)
+    st0 = aff = None
+    if skip is not None:
+        st0, c_skip = _fresh_stats(skip), skip.shape[1]
+        if st0 is None or tuple(skip.shape) != (n, c_skip, 4, 4, 4):
+            raise ValueError('conv3d_e2_level: the skip tensor must be [n, c_skip, 4,4,4] and carry its producer\'s statistics')
+        aff = torch.empty((n, c_skip + cout, 4), dtype=torch.float32, device=x.device)
+    lib.rf_conv3d_e2_level(_p(x), n, c, _p(gn1[0].detach()), _p(gn1[1].detach()), _gn_groups(c, gn1[2]), gn1[3], _p(w1_e2_packed), cmid,
+                           _p(gn2[0].detach()), _p(gn2[1].detach()), _gn_groups(cmid, gn2[2]), gn2[3], _p(w2_e2_packed), cout, _p(out), _p(stats),
+                           _p(st0[0]) if st0 else _p(None), skip.shape[1] if st0 else 0, st0[1] if st0 else 0,
+                           _p(gn_dec[0].detach()) if st0 else _p(None), _p(gn_dec[1].detach()) if st0 else _p(None),
+                           _gn_groups(skip.shape[1] + cout, gn_dec[2]) if st0 else 0, gn_dec[3] if st0 else 0.0, _p(aff), _stream())
+    if aff is not None:
+        out._rf_ready_affine = (aff, out._version, weakref.ref(skip), skip._version, weakref.ref(gn_dec[0]), gn_dec[0]._version,
+                                weakref.ref(gn_dec[1]), gn_dec[1]._version, gn_dec[2], gn_dec[3])
+    return out
+
+
+def _ready_affine(src0, src1, gamma, beta, groups, eps):
+    """the triples of GroupNorm(cat(src0, up2(src1))) if the launch that wrote src1 also wrote them (conv3d_e2_level) for exactly these tensors and
+    parameters, none of them modified since; else None"""
+    r = getattr(src1, '_rf_ready_affine', None) if src0 is not None and src1 is not None else None
+    if r is None:
+        return None
+    aff, v1, ref0, v0, refg, vg, refb, vb, g, e = r
+    same = ref0() is src0 and refg() is gamma and refb() is beta
+    return aff if same and (v1, v0, vg, vb, g, e) == (src1._version, src0._version, gamma._version, beta._version, groups, eps) else None
 
 
 USE_PRESPLIT = True             # False: every layer normalises and splits its own input (the round-2 routes; kept for cross-checks)

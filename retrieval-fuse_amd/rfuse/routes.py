@@ -64,6 +64,25 @@ def pair(n, c0, c1, edge, cmid, cout, groups2, pool, grad, range1, range2, offer
     return 'plain'
 
 
+def level(n, c, edge, cmid, cout, groups1, groups2, grad, range1, range2, skip=None):
+    """A pooling encoder level, MaxPool3d(2) of [n, c, edge^3] -> GroupNorm(groups1) -> conv -> cmid -> GroupNorm(groups2) -> conv -> cout: 'e2_level' where
+    the whole level is one launch (rf_conv3d_e2_level: 4^3 in, both convs on 2^3 volumes), else 'plain' (the max-pool, then ``pair``).  ``skip``: None, or
+    (c_skip, tiles, groups) of the decoder stage that reads the output beside a skip tensor with c_skip channels and that many statistics tiles -- the launch
+    then writes that GroupNorm's table too, or does not take the level.  Only in place of the very launches whose sums it restates: the pair 'plain', both
+    layers 'e2'."""
+    if grad or not ops.USE_E2_LEVEL or ops.CONV_ARITH != 'split' or edge != 4:
+        return 'plain'
+    c_skip, tiles, groups_dec = skip if skip is not None else (0, 0, 0)
+    if not _lib.load_level().rf_conv3d_e2_level_supported(n, c, cmid, cout, groups1, groups2, c_skip, tiles, groups_dec):
+        return 'plain'
+    ok1 = bool(range1())
+    ok2 = ok1 and bool(range2())
+    if not ok2 or pair(n, c, 0, 2, cmid, cout, groups2, None, False, lambda: ok1, lambda: ok2) != 'plain':
+        return 'plain'
+    both_e2 = single(n, c, 0, 2, cmid, None, True, False) == 'e2' and single(n, cmid, 0, 2, cout, None, True, False) == 'e2'
+    return 'e2_level' if both_e2 else 'plain'
+
+
 def head(n, c1, edge, cmid, cout, range1, range2):
     """The final decoder's pair + pointwise head: [n, c1, (edge / 2)^3] upsampled -> cmid -> cout @edge^3 -> 1.  'ch8': both convs, channel-interleaved
     hand-over; 'pointwise': the first as a single layer, the head in the second's epilogue; 'plain': two single layers and the 1x1x1 kernel."""
