@@ -1,6 +1,6 @@
 """ctypes binding of librfuse_hip.so (the C ABI declared in include/rfuse.h, the evaluation ABI of include/rfuse_eval.h, the training-loss ABI
 of include/rfuse_train.h, the contrastive-loss ABI of include/rfuse_contrastive.h, the pairwise-occupancy ABI of include/rfuse_pairs.h, the
-attention-backward ABI of include/rfuse_attn_train.h and the level ABI of include/rfuse_level.h).
+attention-backward ABI of include/rfuse_attn_train.h, the level ABI of include/rfuse_level.h and the dataset ABI of include/rfuse_data.h).
 
 The argument and return types are read from the header itself at import (``parse_header``): there is no second copy of the ABI to keep
 in step.  There is NO fallback: if the library is missing a RuntimeError is raised, and every entry point that returns a status
@@ -12,7 +12,8 @@ first so that the HIP runtime the library binds to is the one PyTorch-ROCm alrea
 rfuse/losses.py) and ``load_contrastive()`` include/rfuse_contrastive.h (``CONTRASTIVE_SIGNATURES``: NT-Xent and the sliced attention contrastive
 loss, rfuse/losses.py) and ``load_pairs()`` include/rfuse_pairs.h (``PAIRS_SIGNATURES``: the retrieval trainer's IoU matrix, rfuse/losses.py) and ``load_attn_train()`` include/rfuse_attn_train.h
 (``ATTN_TRAIN_SIGNATURES``: the backward of the patch attention's row route, rfuse/ops.py) and ``load_level()`` include/rfuse_level.h (``LEVEL_SIGNATURES``:
-a whole encoder level in one launch, rfuse/ops.py), all from the same shared object, under the same status rule.
+a whole encoder level in one launch, rfuse/ops.py) and ``load_data()`` include/rfuse_data.h (``DATA_SIGNATURES``: the patch dataset's occupancy counts and batch
+windows, rfuse/data.py), all from the same shared object, under the same status rule.
 """
 import ctypes
 import os
@@ -30,6 +31,7 @@ CONTRASTIVE_HEADER_PATH = _HERE.parents[1] / 'include' / 'rfuse_contrastive.h'
 PAIRS_HEADER_PATH = _HERE.parents[1] / 'include' / 'rfuse_pairs.h'
 ATTN_TRAIN_HEADER_PATH = _HERE.parents[1] / 'include' / 'rfuse_attn_train.h'
 LEVEL_HEADER_PATH = _HERE.parents[1] / 'include' / 'rfuse_level.h'
+DATA_HEADER_PATH = _HERE.parents[1] / 'include' / 'rfuse_data.h'
 
 # every scalar type include/rfuse.h uses; any pointer is a c_void_p, and `const char*` as a return type a c_char_p
 _SCALARS = {'int': ctypes.c_int, 'float': ctypes.c_float, 'size_t': ctypes.c_size_t, 'int64_t': ctypes.c_int64, 'long long': ctypes.c_int64}
@@ -83,6 +85,7 @@ CONTRASTIVE_SIGNATURES = parse_header(CONTRASTIVE_HEADER_PATH.read_text())
 PAIRS_SIGNATURES = parse_header(PAIRS_HEADER_PATH.read_text())
 ATTN_TRAIN_SIGNATURES = parse_header(ATTN_TRAIN_HEADER_PATH.read_text())
 LEVEL_SIGNATURES = parse_header(LEVEL_HEADER_PATH.read_text())
+DATA_SIGNATURES = parse_header(DATA_HEADER_PATH.read_text())
 
 
 def is_status(name, table=None):
@@ -104,6 +107,7 @@ _contrastive = None
 _pairs = None
 _attn_train = None
 _level = None
+_data = None
 
 
 class _Library:
@@ -205,6 +209,14 @@ def load_level():
     if _level is None:
         _level = _Library(load()._cdll, LEVEL_SIGNATURES)
     return _level
+
+
+def load_data():
+    """The entry points of include/rfuse_data.h, bound like ``load_eval()``'s."""
+    global _data
+    if _data is None:
+        _data = _Library(load()._cdll, DATA_SIGNATURES)
+    return _data
 
 
 def check(rc, what):
