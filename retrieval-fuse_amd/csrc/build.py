@@ -91,7 +91,7 @@ def build(force=False, verbose=False, out=None, extra_flags=(), objdir=None):
     OUT = Path(out) if out is not None else globals()['OUT']
     objdir = Path(objdir) if objdir is not None else HERE / 'build'
     objdir.mkdir(exist_ok=True, parents=True)
-    headers = [HERE / 'common.h', HERE / 'conv_box.h', HERE / 'conv_split_common.h', HERE / 'conv_split_args.h', HERE / 'split_operand.h', HERE / 'attn_row.h', HERE / 'philox.h',
+    headers = [HERE / 'common.h', HERE / 'lane_reduce.h', HERE / 'conv_box.h', HERE / 'conv_split_common.h', HERE / 'conv_split_args.h', HERE / 'split_operand.h', HERE / 'attn_row.h', HERE / 'philox.h',
                HERE.parents[1] / 'include' / 'rfuse.h', HERE.parents[1] / 'include' / 'rfuse_eval.h', HERE.parents[1] / 'include' / 'rfuse_train.h',
                HERE.parents[1] / 'include' / 'rfuse_contrastive.h', HERE.parents[1] / 'include' / 'rfuse_pairs.h', HERE.parents[1] / 'include' / 'rfuse_attn_train.h',
                HERE.parents[1] / 'include' / 'rfuse_level.h', HERE.parents[1] / 'include' / 'rfuse_data.h']
@@ -130,8 +130,8 @@ TESTKIT_OUT = TESTKIT_SRC.parent / 'librfuse_testkit.so'
 
 
 def build_testkit(force=False):
-    """tests/testkit/librfuse_testkit.so: the test harness's own kernels (NaN poisoning of LDS / VGPRs, an F16-MFMA load).  Kept out of the product ABI."""
-    if force or _stale(TESTKIT_OUT, [TESTKIT_SRC, HERE / 'build.py']):
+    """tests/testkit/librfuse_testkit.so: the test harness's own kernels (NaN poisoning of LDS / VGPRs, an F16-MFMA load, a probe of lane_reduce.h).  Kept out of the product ABI."""
+    if force or _stale(TESTKIT_OUT, [TESTKIT_SRC, HERE / 'lane_reduce.h', HERE / 'build.py']):
         subprocess.run([_hipcc(), '--offload-arch=gfx950', '-O3', '-std=c++17', '-shared', '-fPIC', '-o', str(TESTKIT_OUT), str(TESTKIT_SRC)], check=True)
     return TESTKIT_OUT
 

@@ -5,7 +5,7 @@
 #include <stdio.h>
 #include "../../include/rfuse.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "lane_reduce.h"      // f32x4, wave_sum / wave_max, rf_max / rf_relu and the fixed-order reductions of the epilogues
 
 void rf_set_error(const char* fmt, ...);
 
@@ -117,22 +117,7 @@ __device__ __forceinline__ unsigned rf_xcd_contiguous(unsigned b, unsigned g) {
     return k * per + (k < rem ? k : rem) + (b >> 3);
 }
 
-// wave64 sum reduction; result valid in every lane
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-// Max, ReLU and the split operands' f16-range clamp of the forward kernels, NaN-propagating like the reference (torch.relu, F.max_pool3d, fp32
-// arithmetic).  fmaxf is IEEE maxNum (v_max_f32): given one NaN it returns the other operand, so a NaN accumulator came out of a ReLU as 0 and out
-// of a max-pool as its neighbours' maximum; v_med3_f32 returns a bound for a NaN input.  For finite inputs these give the same bits as before.
-__device__ __forceinline__ float rf_max(float a, float b) { return __builtin_elementwise_maximum(a, b); }      // IEEE-754-2019 maximum: v_maximum3_f32
-__device__ __forceinline__ float rf_relu(float v) { return __builtin_elementwise_maximum(v, 0.f); }
+// The split operands' f16-range clamp, NaN-propagating like rf_max / rf_relu (lane_reduce.h); v_med3_f32 alone returns a bound for a NaN input.
 // clamp to [-65504, 65504]; NaN and +-inf come out as NaN.  0 * v is NaN for those and a zero of v's sign otherwise, and adding a zero of
 // v's sign to med3(v, ...) changes no finite result (-0 included): two VALU ops (v_med3_f32 + v_fma_f32), the f16 split after it keeps the NaN.
 // The fma is inline asm: as fmaf the compiler pairs it into v_pk_fma_f32 with op_sel on src1, which build.py:check_isa refuses
@@ -141,13 +126,6 @@ __device__ __forceinline__ float rf_clamp_f16(float v) {
     float r;
     asm("v_fma_f32 %0, %1, 0, %2" : "=v"(r) : "v"(v), "v"(m));
     return r;
-}
-
-// fmaxf (maxNum) on purpose: only the top-k scan's seed bound uses this (retrieval.hip), no forward activation does
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
 }
 
 // GroupNorm as the conv kernels apply it: y = (x - center) * scale + shift with, per (sample, channel),

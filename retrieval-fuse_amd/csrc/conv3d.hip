@@ -265,8 +265,7 @@ __global__ __launch_bounds__(256) void k_maxpool2_small(const float* __restrict_
     }
     if (stats) {
         double sm = (double)m, sq = (double)m * m;
-#pragma unroll
-        for (int d = OV >> 1; d > 0; d >>= 1) { sm += __shfl_xor(sm, d, 64); sq += __shfl_xor(sq, d, 64); }
+        rf_xor_sum2<(OV >> 1), 1>(sm, sq);                             // halving: OV / 2, .. 1
         if (live && o == 0) stats[plane] = make_double2(sm, sq);
     }
     (void)PPW;

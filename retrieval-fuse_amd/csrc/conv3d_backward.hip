@@ -44,8 +44,7 @@ __global__ __launch_bounds__(256) void k_relu_bwd_amax(const float4* __restrict_
         bad = bad || !(fabsf(o.x) < INFINITY) || !(fabsf(o.y) < INFINITY) || !(fabsf(o.z) < INFINITY) || !(fabsf(o.w) < INFINITY);
     }
     if (bad) m = INFINITY;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) m = fmaxf(m, __shfl_xor(m, d, 64));
+    m = wave_max(m);
     __shared__ float wm[4];
     if ((threadIdx.x & 63) == 0) wm[threadIdx.x >> 6] = m;
     __syncthreads();
@@ -71,8 +70,7 @@ extern "C" int rf_relu_backward_amax(const float* dy, const float* y, size_t cou
 __global__ __launch_bounds__(256) void k_dgrad_affine(const float* __restrict__ slots, int rows, float4* __restrict__ affine, float* __restrict__ scales) {
     float m = 0.f;
     for (int k = threadIdx.x; k < RF_AMAX_SLOTS; k += 256) m = fmaxf(m, slots[k]);
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) m = fmaxf(m, __shfl_xor(m, d, 64));
+    m = wave_max(m);
     __shared__ float wm[4];
     if ((threadIdx.x & 63) == 0) wm[threadIdx.x >> 6] = m;
     __syncthreads();
@@ -225,7 +223,7 @@ __global__ __launch_bounds__(256) void k_gnb_partial(const float* __restrict__ x
             }
         }
     }
-    const int span = L < 64 ? L : 64;
+    const int span = L < 64 ? L : 64;                               // (rf_xor_sum2 of lane_reduce.h is this butterfly for two values and a compile-time span)
     for (int d = span >> 1; d >= 1; d >>= 1) {
         sx += __shfl_xor(sx, d, 64); sq += __shfl_xor(sq, d, 64); sd += __shfl_xor(sd, d, 64); sdx += __shfl_xor(sdx, d, 64);
     }

@@ -200,10 +200,7 @@ __global__ __launch_bounds__(256, 2) void k_conv3_e2_split(E2Args a) {
                 if (live) a.out[(size_t)sm * ncols + col] = y;
                 if (a.stats) {                                      // the 8 voxels of a cout: lanes li & 7 = 0 .. 7 of the same row (wave-uniform branch)
                     double sv = (double)y, sq = (double)y * (double)y;
-                    if constexpr (V == 8) {
-#pragma unroll
-                        for (int d = 1; d <= 4; d <<= 1) { sv += __shfl_xor(sv, d, 64); sq += __shfl_xor(sq, d, 64); }
-                    }
+                    if constexpr (V == 8) rf_xor_sum2<1, 4>(sv, sq);
                     if (live && (V == 1 || (li & 7) == 0)) a.stats[(size_t)sm * cout + (V == 8 ? col >> 3 : col)] = make_double2(sv, sq);
                 }
             }

@@ -401,35 +401,10 @@ __global__ __launch_bounds__(256) void k_conv3_cin1(ConvArgs a) {
         }
     }
     __syncthreads();
-    // cout PAIRS per accumulator register pair: v_pk_fma_f32 (two fp32 FMAs per lane and issue -- the 157 TFLOP/s vector peak is the packed
-    // rate); per output the taps are still accumulated one by one in (dy, dx, dz) order, each with a single rounding
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
+    // cout pairs on v_pk_fma_f32, taps accumulated in (dy, dx, dz) order: rf_cin1_taps (lane_reduce.h)
     constexpr int CP = (COUT + 1) / 2;
     f32x2 acc2[TZ][CP];
-#pragma unroll
-    for (int z = 0; z < TZ; ++z)
-#pragma unroll
-        for (int cp = 0; cp < CP; ++cp) acc2[z][cp] = (f32x2){0.f, 0.f};
-#pragma unroll
-    for (int dy = 0; dy < 3; ++dy)
-#pragma unroll
-        for (int dx = 0; dx < 3; ++dx) {
-            float col[HZ];
-#pragma unroll
-            for (int hz = 0; hz < HZ; ++hz) col[hz] = xs[(hz * HY + (y + dy)) * HX + x + dx];
-#pragma unroll
-            for (int dz = 0; dz < 3; ++dz) {
-                const float4 w0 = *reinterpret_cast<const float4*>(wl + ((dz * 3 + dy) * 3 + dx) * 8);
-                const float4 w1 = *reinterpret_cast<const float4*>(wl + ((dz * 3 + dy) * 3 + dx) * 8 + 4);
-                const f32x2 wv[4] = {(f32x2){w0.x, w0.y}, (f32x2){w0.z, w0.w}, (f32x2){w1.x, w1.y}, (f32x2){w1.z, w1.w}};
-#pragma unroll
-                for (int z = 0; z < TZ; ++z) {
-                    const f32x2 c2 = (f32x2){col[z + dz], col[z + dz]};
-#pragma unroll
-                    for (int cp = 0; cp < CP; ++cp) acc2[z][cp] = __builtin_elementwise_fma(c2, wv[cp], acc2[z][cp]);
-                }
-            }
-        }
+    rf_cin1_taps<TZ, CP, HY * HX, HX>(xs + y * HX + x, wl, acc2);
     float acc[TZ][COUT];
 #pragma unroll
     for (int z = 0; z < TZ; ++z)
@@ -444,8 +419,7 @@ __global__ __launch_bounds__(256) void k_conv3_cin1(ConvArgs a) {
     }
     if (a.stats) {
         // per (wave, cout) sums of the ReLU'd outputs in float64.  The 16 values of a lane (sum and sum of squares of 8 couts) are reduced over
-        // the wave by recursive halving: at step k a lane keeps half of its values and hands the other half to lane ^ (1 << k) -- 17 value
-        // exchanges instead of 16 x 6 (the per-value butterflies were a quarter of the kernel's instructions); fixed order, no atomics
+        // the wave by recursive halving (rf_transpose_sum16: the per-value butterflies were a quarter of the kernel's instructions); fixed order, no atomics
         __shared__ double red[4 * 16];
         const int lane = tid & 63, wave = tid >> 6;
         double v[16];
@@ -461,22 +435,8 @@ __global__ __launch_bounds__(256) void k_conv3_cin1(ConvArgs a) {
             }
             v[2 * co] = sm; v[2 * co + 1] = sq;
         }
-        auto halve = [&](auto kc) {
-            constexpr int K = decltype(kc)::value, C = 8 >> K;
-            const bool up = (lane >> K) & 1;
-#pragma unroll
-            for (int i = 0; i < C; ++i) {
-                const double send = up ? v[i] : v[i + C], keep = up ? v[i + C] : v[i];
-                v[i] = keep + __shfl_xor(send, 1 << K, 64);
-            }
-        };
-        halve(std::integral_constant<int, 0>{});
-        halve(std::integral_constant<int, 1>{});
-        halve(std::integral_constant<int, 2>{});
-        halve(std::integral_constant<int, 3>{});
-        v[0] += __shfl_xor(v[0], 16, 64);
-        v[0] += __shfl_xor(v[0], 32, 64);
-        if (lane < 16) red[wave * 16 + ((lane & 1) * 8 + ((lane >> 1) & 1) * 4 + ((lane >> 2) & 1) * 2 + ((lane >> 3) & 1))] = v[0];
+        const double tot = rf_transpose_sum16(v, lane);
+        if (lane < 16) red[wave * 16 + rf_transpose_slot16(lane)] = tot;
         __syncthreads();
         if (tid < COUT) {
             double sm = 0.0, sq = 0.0;

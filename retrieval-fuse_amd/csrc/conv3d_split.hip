@@ -523,32 +523,8 @@ __global__ __launch_bounds__(512, 4) void k_conv3_cin1_presplit(Cin1PreArgs a) {
     }
     __syncthreads();
     const int x = tid & 15, y = (tid >> 4) & 15, z0 = (tid >> 8) * 8;
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
     f32x2 acc2[8][4];
-#pragma unroll
-    for (int z = 0; z < 8; ++z)
-#pragma unroll
-        for (int cp = 0; cp < 4; ++cp) acc2[z][cp] = (f32x2){0.f, 0.f};
-#pragma unroll
-    for (int dy = 0; dy < 3; ++dy)
-#pragma unroll
-        for (int dx = 0; dx < 3; ++dx) {
-            float col[10];
-#pragma unroll
-            for (int hz = 0; hz < 10; ++hz) col[hz] = xs[(z0 + hz) * (H * H) + (y + dy) * H + x + dx];
-#pragma unroll
-            for (int dz = 0; dz < 3; ++dz) {
-                const float4 w0 = *reinterpret_cast<const float4*>(wl + ((dz * 3 + dy) * 3 + dx) * 8);
-                const float4 w1 = *reinterpret_cast<const float4*>(wl + ((dz * 3 + dy) * 3 + dx) * 8 + 4);
-                const f32x2 wv[4] = {(f32x2){w0.x, w0.y}, (f32x2){w0.z, w0.w}, (f32x2){w1.x, w1.y}, (f32x2){w1.z, w1.w}};
-#pragma unroll
-                for (int z = 0; z < 8; ++z) {
-                    const f32x2 c2 = (f32x2){col[z + dz], col[z + dz]};
-#pragma unroll
-                    for (int cp = 0; cp < 4; ++cp) acc2[z][cp] = __builtin_elementwise_fma(c2, wv[cp], acc2[z][cp]);
-                }
-            }
-        }
+    rf_cin1_taps<8, 4, H * H, H>(xs + z0 * (H * H) + y * H + x, wl, acc2);
     float act[8][8];                                                // ReLU'd outputs [z][cout]
 #pragma unroll
     for (int z = 0; z < 8; ++z)
@@ -563,22 +539,8 @@ __global__ __launch_bounds__(512, 4) void k_conv3_cin1_presplit(Cin1PreArgs a) {
             for (int z = 0; z < 8; ++z) { const double t = (double)act[z][co]; sm += t; sq += t * t; }
             v[2 * co] = sm; v[2 * co + 1] = sq;
         }
-        auto halve = [&](auto kc) {
-            constexpr int K = decltype(kc)::value, C = 8 >> K;
-            const bool up = (lane >> K) & 1;
-#pragma unroll
-            for (int i = 0; i < C; ++i) {
-                const double send = up ? v[i] : v[i + C], keep = up ? v[i + C] : v[i];
-                v[i] = keep + __shfl_xor(send, 1 << K, 64);
-            }
-        };
-        halve(std::integral_constant<int, 0>{});
-        halve(std::integral_constant<int, 1>{});
-        halve(std::integral_constant<int, 2>{});
-        halve(std::integral_constant<int, 3>{});
-        v[0] += __shfl_xor(v[0], 16, 64);
-        v[0] += __shfl_xor(v[0], 32, 64);
-        if (lane < 16) red[wave * 16 + ((lane & 1) * 8 + ((lane >> 1) & 1) * 4 + ((lane >> 2) & 1) * 2 + ((lane >> 3) & 1))] = v[0];
+        const double tot = rf_transpose_sum16(v, lane);
+        if (lane < 16) red[wave * 16 + rf_transpose_slot16(lane)] = tot;
     }
     __syncthreads();
     if (tid < 8) {                                                  // the consumer's GroupNorm triple of channel tid

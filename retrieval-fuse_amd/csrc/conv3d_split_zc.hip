@@ -187,25 +187,15 @@ __global__ __launch_bounds__(512, 4) void k_conv3_split_zc(ConvArgs a, SplitPreO
                         make_float4(rf_max(v[0], a.floor), rf_max(v[1], a.floor), rf_max(v[2], a.floor), rf_max(v[3], a.floor));
                 }
             }
-            if (a.stats) {
-#pragma unroll
-                for (int m = 0; m < 4; ++m)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) { const double v = (double)rf_relu(acc[m][r]); fsm += v; fsq += v * v; }
-            }
+            if (a.stats) rf_relu_sums(acc, fsm, fsq);
         }
         if (want_pool) {                                              // z pair = planes (2 zp, 2 zp + 1), x pairs in r, y pair in lane ^ 32
 #pragma unroll
             for (int zp = 0; zp < 2; ++zp) {
-                const f32x4 u = acc[2 * zp], v = acc[2 * zp + 1];
-                float p0 = rf_max(rf_max(u[0], u[1]), rf_max(v[0], v[1]));
-                float p1 = rf_max(rf_max(u[2], u[3]), rf_max(v[2], v[3]));
-                p0 = rf_max(p0, __shfl_xor(p0, 32, 64));
-                p1 = rf_max(p1, __shfl_xor(p1, 32, 64));
-                p0 = rf_relu(p0);                                  // max and ReLU commute
-                p1 = rf_relu(p1);
+                float p0, p1;
+                rf_pool_cell(acc[2 * zp], acc[2 * zp + 1], p0, p1);
                 pooled[zp] = make_float2(p0, p1);
-                if (kq < 2) { psm += (double)p0 + (double)p1; psq += (double)p0 * (double)p0 + (double)p1 * (double)p1; }
+                if (kq < 2) rf_pool_sums(p0, p1, psm, psq);
             }
         }
     };
@@ -246,13 +236,12 @@ __global__ __launch_bounds__(512, 4) void k_conv3_split_zc(ConvArgs a, SplitPreO
         }
         if (sample_end) {
             if (a.pool_stats || po.out) {                              // (the hand-over needs the pooled sample's sums whether or not the caller wants them)
-                const double s1 = psm + __shfl_xor(psm, 16, 64), s2 = psq + __shfl_xor(psq, 16, 64);      // the two x halves (lane groups 0 and 1)
-                if (lane < 16) red[wave * 16 + lane] = make_double2(s1, s2);
+                rf_xor_sum2<16, 16>(psm, psq);                         // the two x halves (lane groups 0 and 1)
+                if (lane < 16) red[wave * 16 + lane] = make_double2(psm, psq);
             }
             if (FULL && a.stats) {
-                double s1 = fsm + __shfl_xor(fsm, 16, 64), s2 = fsq + __shfl_xor(fsq, 16, 64);
-                s1 += __shfl_xor(s1, 32, 64); s2 += __shfl_xor(s2, 32, 64);
-                if (lane < 16) red[128 + wave * 16 + lane] = make_double2(s1, s2);
+                rf_xor_sum2<16, 32>(fsm, fsq);
+                if (lane < 16) red[128 + wave * 16 + lane] = make_double2(fsm, fsq);
             }
             fsm = fsq = psm = psq = 0.0;
         }
@@ -534,27 +523,16 @@ __global__ __launch_bounds__(512, 4) void k_conv3_split_zcm(ConvArgs a, SplitPre
                         for (int m = 0; m < 4; ++m)
                             *reinterpret_cast<float4*>(o + (o0 + (unsigned)(m * edge * edge))) = make_float4(hi[m][0], hi[m][1], hi[m][2], hi[m][3]);
                     }
-                    if (a.stats) {
-#pragma unroll
-                        for (int m = 0; m < 4; ++m)
-#pragma unroll
-                            for (int r = 0; r < 4; ++r) { const double v = (double)rf_relu(hi[m][r]); fsm += v; fsq += v * v; }
-                    }
+                    if (a.stats) rf_relu_sums(hi, fsm, fsq);
                 }
                 if (a.pool_mode) {                                    // fused MaxPool3d(2): z pair = planes (2 zp, 2 zp + 1), x pairs in r, y pair in lane ^ 32
                     const int hedge = edge >> 1;
 #pragma unroll
                     for (int zp = 0; zp < 2; ++zp) {
-                        const f32x4 u = hi[2 * zp], v = hi[2 * zp + 1];
-                        float p0 = rf_max(rf_max(u[0], u[1]), rf_max(v[0], v[1]));
-                        float p1 = rf_max(rf_max(u[2], u[3]), rf_max(v[2], v[3]));
-                        p0 = rf_max(p0, __shfl_xor(p0, 32, 64));
-                        p1 = rf_max(p1, __shfl_xor(p1, 32, 64));
-                        p0 = rf_relu(p0);                          // max and ReLU commute
-                        p1 = rf_relu(p1);
+                        float p0, p1;
+                        rf_pool_cell(hi[2 * zp], hi[2 * zp + 1], p0, p1);
                         if (kq < 2) {
-                            psm += (double)p0 + (double)p1;
-                            psq += (double)p0 * (double)p0 + (double)p1 * (double)p1;
+                            rf_pool_sums(p0, p1, psm, psq);
                             if (co_g < a.cout)
                                 *reinterpret_cast<float2*>(a.pool_out + (size_t)n0 * a.cout * ((size_t)hedge * hedge * hedge) +
                                                            ((unsigned)co_g * (unsigned)(hedge * hedge * hedge) +
@@ -572,12 +550,11 @@ __global__ __launch_bounds__(512, 4) void k_conv3_split_zcm(ConvArgs a, SplitPre
                     // statistics of the box: lane -> lane groups -> waves through the dead image, fixed order, float64
                     double2* red = reinterpret_cast<double2*>(img);
                     if (a.stats) {
-                        fsm += __shfl_xor(fsm, 16, 64); fsq += __shfl_xor(fsq, 16, 64);
-                        fsm += __shfl_xor(fsm, 32, 64); fsq += __shfl_xor(fsq, 32, 64);
+                        rf_xor_sum2<16, 32>(fsm, fsq);
                         if (lane < 16) red[wave * 16 + lane] = make_double2(fsm, fsq);
                     }
                     if (a.pool_stats) {
-                        psm += __shfl_xor(psm, 16, 64); psq += __shfl_xor(psq, 16, 64);      // the two x halves (lane groups 0 and 1)
+                        rf_xor_sum2<16, 16>(psm, psq);                     // the two x halves (lane groups 0 and 1)
                         if (lane < 16) red[128 + wave * 16 + lane] = make_double2(psm, psq);
                     }
                     lds_barrier();

@@ -815,25 +815,14 @@ __global__ __launch_bounds__(512, 4) void k_conv3_up(UpArgs a) {
             if (SPW == 1) {
                 double sm = 0.0, sq = 0.0;
 #pragma unroll
-                for (int mb = 0; mb < MB; ++mb)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const double v = (double)rf_relu(acc[mb][nb][r]);
-                        sm += v; sq += v * v;
-                    }
-                sm += __shfl_xor(sm, 16, 64); sq += __shfl_xor(sq, 16, 64);
-                sm += __shfl_xor(sm, 32, 64); sq += __shfl_xor(sq, 32, 64);
+                for (int mb = 0; mb < MB; ++mb) rf_relu_sums(acc[mb][nb], sm, sq);
+                rf_xor_sum2<16, 32>(sm, sq);
                 if (lane_e < 16) { red[(wave * 16 + lane_e) * 2] = sm; red[(wave * 16 + lane_e) * 2 + 1] = sq; }
             } else {
                 // T = 4, four samples: voxel v = mb*16 + 4*kq + r belongs to sample kq (both m-blocks = lattice planes)
                 double sm = 0.0, sq = 0.0;
 #pragma unroll
-                for (int mb = 0; mb < MB; ++mb)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const double v = (double)rf_relu(acc[mb][nb][r]);
-                        sm += v; sq += v * v;
-                    }
+                for (int mb = 0; mb < MB; ++mb) rf_relu_sums(acc[mb][nb], sm, sq);
                 red[((wave * SPW + kq) * 16 + li) * 2] = sm;
                 red[((wave * SPW + kq) * 16 + li) * 2 + 1] = sq;
             }
@@ -884,13 +873,8 @@ __global__ __launch_bounds__(512, 4) void k_conv3_up(UpArgs a) {
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
                 double sm = 0.0, sq = 0.0;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const double v = (double)rf_relu(acc4[h][i]);
-                    sm += v; sq += v * v;
-                }
-#pragma unroll
-                for (int m = 4; m < 64; m <<= 1) { sm += __shfl_xor(sm, m, 64); sq += __shfl_xor(sq, m, 64); }
+                rf_relu_sums(acc4[h], sm, sq);
+                rf_xor_sum2<4, 32>(sm, sq);
                 if (lane_e < 4) { red[(wave * 8 + 4 * h + lane_e) * 2] = sm; red[(wave * 8 + 4 * h + lane_e) * 2 + 1] = sq; }
             }
             __syncthreads();

@@ -196,8 +196,7 @@ __device__ __forceinline__ double2 us_box_channel_sums(const float* e, int co, i
             sm += (double)v.w; sq += (double)v.w * v.w;
         }
     }
-#pragma unroll
-    for (int msk = 1; msk < 8; msk <<= 1) { sm += __shfl_xor(sm, msk, 64); sq += __shfl_xor(sq, msk, 64); }
+    rf_xor_sum2<1, 4>(sm, sq);
     return make_double2(sm, sq);
 }
 
@@ -465,7 +464,8 @@ __device__ __forceinline__ double pp_dpp_f64(double v) {
     return __hiloint2double(hi_, lo_);
 }
 // 8 values per lane, summed over the 16 lanes of a DPP row: a butterfly that halves the value count per level (partner lanes n ^ 15, n ^ 7, n ^ 2: every partner
-// agrees with the lane on the bits already used), then one plain exchange with lane n ^ 1 -- lanes n and n ^ 1 end up with the row's total of value n >> 1
+// agrees with the lane on the bits already used), then one plain exchange with lane n ^ 1 -- lanes n and n ^ 1 end up with the row's total of value n >> 1.
+// Sibling of rf_transpose_sum16 (lane_reduce.h): another partner order, on DPP, so it stays here
 __device__ __forceinline__ double pp_row16_transpose_sum8(double (&d)[8], int n) {
 #define PP_LEVEL(W_, CTRL_, BIT_)                                                                   \
     {                                                                                               \
@@ -1107,7 +1107,7 @@ __global__ __launch_bounds__(512, NB >= 3 ? 2 : 4) void k_conv3_up_split_s4(UpSp
                 s += (double)v.z; sq += (double)v.z * v.z;
                 s += (double)v.w; sq += (double)v.w * v.w;
             }
-            s += __shfl_xor(s, 1, 64); sq += __shfl_xor(sq, 1, 64);
+            rf_xor_sum2<1, 1>(s, sq);
             if (part == 0 && co < NB * 16 && cob + co < cout && n0 + sm < a.n) a.stats[(size_t)(n0 + sm) * cout + cob + co] = make_double2(s, sq);
         }
     }

@@ -97,14 +97,8 @@ __device__ __forceinline__ void conv_box_epilogue(const ConvArgs& a, f32x4 (&acc
             if (SLOTS == 1) {
                 double sm = 0.0, sq = 0.0;
 #pragma unroll
-                for (int mb = 0; mb < MB; ++mb)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const double v = (double)rf_relu(acc[mb][nb][r]);
-                        sm += v; sq += v * v;
-                    }
-                sm += __shfl_xor(sm, 16, 64); sq += __shfl_xor(sq, 16, 64);
-                sm += __shfl_xor(sm, 32, 64); sq += __shfl_xor(sq, 32, 64);
+                for (int mb = 0; mb < MB; ++mb) rf_relu_sums(acc[mb][nb], sm, sq);
+                rf_xor_sum2<16, 32>(sm, sq);
                 if (lane < 16) {
                     red[((size_t)wave * NCO + nb * 16 + lane) * 2] = sm;
                     red[((size_t)wave * NCO + nb * 16 + lane) * 2 + 1] = sq;
@@ -113,12 +107,8 @@ __device__ __forceinline__ void conv_box_epilogue(const ConvArgs& a, f32x4 (&acc
 #pragma unroll
                 for (int mb = 0; mb < MB; ++mb) {
                     double sm = 0.0, sq = 0.0;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const double v = (double)rf_relu(acc[mb][nb][r]);
-                        sm += v; sq += v * v;
-                    }
-                    sm += __shfl_xor(sm, 16, 64); sq += __shfl_xor(sq, 16, 64);      // lanes {0..31}: sample 2mb, {32..63}: 2mb+1
+                    rf_relu_sums(acc[mb][nb], sm, sq);
+                    rf_xor_sum2<16, 16>(sm, sq);                                     // lanes {0..31}: sample 2mb, {32..63}: 2mb+1
                     if ((lane & 16) == 0) {
                         const int slot = mb * 2 + (lane >> 5);
                         red[(((size_t)wave * SLOTS + slot) * NCO + nb * 16 + (lane & 15)) * 2] = sm;
@@ -165,14 +155,10 @@ __device__ __forceinline__ void conv_box_epilogue(const ConvArgs& a, f32x4 (&acc
                 double sm = 0.0, sq = 0.0;
 #pragma unroll
                 for (int yh = 0; yh < 2; ++yh) {
-                    const f32x4 u = acc[2 * yh][nb], v = acc[2 * yh + 1][nb];
-                    float p0 = rf_max(rf_max(u[0], u[1]), rf_max(v[0], v[1]));
-                    float p1 = rf_max(rf_max(u[2], u[3]), rf_max(v[2], v[3]));
-                    p0 = rf_max(p0, __shfl_xor(p0, 32, 64));
-                    p1 = rf_max(p1, __shfl_xor(p1, 32, 64));
-                    p0 = rf_relu(p0);                        // max and ReLU commute
-                    p1 = rf_relu(p1);
+                    float p0, p1;
+                    rf_pool_cell(acc[2 * yh][nb], acc[2 * yh + 1][nb], p0, p1);
                     if (kq < 2) {
+                        // rf_pool_sums and, below, rf_xor_sum2<16, 16> written out: through either k_conv3_split<1, 6, true, ..> (80 VGPRs) spills 2-4 registers
                         sm += (double)p0 + (double)p1;
                         sq += (double)p0 * (double)p0 + (double)p1 * (double)p1;
                         if (co < a.cout) {

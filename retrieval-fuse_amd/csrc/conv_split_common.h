@@ -97,8 +97,7 @@ __device__ __forceinline__ double2 rf_tile_channel_sums(const float* e, int co, 
             sm += (double)v; sq += (double)v * v;
         }
     }
-#pragma unroll
-    for (int msk = 1; msk < TPC; msk <<= 1) { sm += __shfl_xor(sm, msk, 64); sq += __shfl_xor(sq, msk, 64); }
+    rf_xor_sum2<1, TPC / 2>(sm, sq);
     return make_double2(sm, sq);
 }
 

@@ -176,8 +176,7 @@ __global__ __launch_bounds__(256) void k_minplus(int B, int D, int H, int W, con
         const int v = min(best[j] + a * a, kInf);
         if (((qmask >> j) & 1u) && v < kInf) s += v;                   // an empty source grid leaves every value at kInf: its sum stays 0
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    s = wave_sum(s);
     if (tx == 0) part[r] = s;
     __syncthreads();
     if (threadIdx.x == 0) {

@@ -110,11 +110,6 @@ __device__ __forceinline__ void similarities(double* sA, double* sB, const doubl
         }
     }
 }
-__device__ __forceinline__ double wave_max_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-    return v;
-}
 }   // namespace
 
 __global__ __launch_bounds__(kPlanThreads) void k_ntx_plan(const uint8_t* __restrict__ occ, int n_rows, int num_slices, int max_rows, int tiles_max, int* __restrict__ hdr,
@@ -221,7 +216,7 @@ __global__ __launch_bounds__(kThreads) void k_ntx_lse(const float* __restrict__ 
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const int i = i0 + 4 * wv + r;
-        const double top = wave_max_d(m[r]);                              // some lane holds the positive: finite unless the logits are not
+        const double top = wave_max(m[r]);                              // some lane holds the positive: finite unless the logits are not
         const double part = sum[r] == 0.0 ? 0.0 : sum[r] * exp(m[r] - top);      // a lane without a column: (max, sum) = (-inf, 0)
         const double all = wave_sum(part), lp = wave_sum(lpos[r]);
         if (lane == 0 && i < n2) {

@@ -18,6 +18,7 @@ def load():
         _lib.rft_poison_lds.argtypes = [ctypes.c_void_p]
         _lib.rft_poison_vgprs.argtypes = [ctypes.c_void_p]
         _lib.rft_f16_mfma_load.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+        _lib.rft_lane_reduce_probe.argtypes = [ctypes.c_void_p] * 6
     return _lib
 
 
@@ -27,3 +28,17 @@ def f16_mfma_load(stream, out, blocks=256, iters=60000):
     rc = load().rft_f16_mfma_load(blocks, iters, out.data_ptr(), stream.cuda_stream)
     if rc != 0:
         raise RuntimeError('rft_f16_mfma_load: HIP error %d' % rc)
+
+
+def lane_reduce_probe(din, fin):
+    """One wave runs the helpers of csrc/lane_reduce.h: din [64, 18] float64 and fin [64, 8] float32 on the GPU -> (dout [64, 11], fout [64, 2], iout [64]);
+    the columns are described at k_lane_reduce_probe (testkit.hip)."""
+    assert din.shape == (64, 18) and din.dtype == torch.float64 and din.is_contiguous() and din.is_cuda
+    assert fin.shape == (64, 8) and fin.dtype == torch.float32 and fin.is_contiguous() and fin.is_cuda
+    dout = torch.empty(64, 11, dtype=torch.float64, device=din.device)
+    fout = torch.empty(64, 2, dtype=torch.float32, device=din.device)
+    iout = torch.empty(64, dtype=torch.int32, device=din.device)
+    rc = load().rft_lane_reduce_probe(din.data_ptr(), fin.data_ptr(), dout.data_ptr(), fout.data_ptr(), iout.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    if rc != 0:
+        raise RuntimeError('rft_lane_reduce_probe: HIP error %d' % rc)
+    return dout, fout, iout
