@@ -74,7 +74,8 @@ static inline unsigned rf_blocks(size_t total, size_t per_block, size_t cap) {
 }
 
 // out[i] = (float)(sum over g = 0..slices-1, in that order, of (double)parts[g * count + i]): the end of every split-K weight gradient whose slices
-// are plain fp32 partials (rf_conv3d_k3_wgrad, rf_conv3d_valid_wgrad, rf_linear_wgrad).  Deterministic, no atomics.  Defined in conv3d_backward.hip.
+// are plain fp32 partials (rf_conv3d_k3_wgrad, rf_conv3d_valid_wgrad, rf_linear_wgrad) and of the valid conv's bias gradient
+// (rf_conv3d_valid_leaky_backward).  Deterministic, no atomics.  Defined in conv3d_backward.hip.
 int rf_slice_sum(const float* parts, int slices, size_t count, float* out, hipStream_t stream, const char* who);
 
 static inline bool rf_is_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }

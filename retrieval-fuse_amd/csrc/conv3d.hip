@@ -86,17 +86,10 @@ __global__ __launch_bounds__(256) void k_gn_partial(const float* __restrict__ sr
         sum += wgt * ls;
         sq += wgt * lq;
     }
-    sum = wave_sum(sum);
-    sq = wave_sum(sq);
-    __shared__ double red[8];
-    const int wave = tid >> 6, lane = tid & 63;
-    if (lane == 0) { red[wave * 2] = sum; red[wave * 2 + 1] = sq; }
-    __syncthreads();
-    if (tid == 0) {
-        double a = 0.0, b = 0.0;
-        for (int w = 0; w < 4; ++w) { a += red[w * 2]; b += red[w * 2 + 1]; }
-        part[(size_t)ng * slices + s] = make_double2(a, b);
-    }
+    __shared__ double red[4][2];
+    rf_waves_put(red, {wave_sum(sum), wave_sum(sq)});
+    // 0.0 +: this sum used to start from 0.0, which turns all-(-0.0) wave totals into +0.0
+    if (tid == 0) part[(size_t)ng * slices + s] = make_double2(0.0 + rf_waves_sum(red, 0), 0.0 + rf_waves_sum(red, 1));
 }
 
 // pass 2: fixed-order reduction of the slices, then the affine triple per (n, c)

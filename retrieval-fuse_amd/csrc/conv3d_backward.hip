@@ -44,12 +44,10 @@ __global__ __launch_bounds__(256) void k_relu_bwd_amax(const float4* __restrict_
         bad = bad || !(fabsf(o.x) < INFINITY) || !(fabsf(o.y) < INFINITY) || !(fabsf(o.z) < INFINITY) || !(fabsf(o.w) < INFINITY);
     }
     if (bad) m = INFINITY;
-    m = wave_max(m);
-    __shared__ float wm[4];
-    if ((threadIdx.x & 63) == 0) wm[threadIdx.x >> 6] = m;
-    __syncthreads();
+    __shared__ float wm[4][1];
+    rf_waves_put(wm, {wave_max(m)});
     if (threadIdx.x == 0) {
-        slots[blockIdx.x] = fmaxf(fmaxf(wm[0], wm[1]), fmaxf(wm[2], wm[3]));
+        slots[blockIdx.x] = rf_waves_max(wm);
         for (unsigned k = blockIdx.x + gridDim.x; k < (unsigned)RF_AMAX_SLOTS; k += gridDim.x) slots[k] = 0.f;
     }
 }
@@ -70,11 +68,9 @@ extern "C" int rf_relu_backward_amax(const float* dy, const float* y, size_t cou
 __global__ __launch_bounds__(256) void k_dgrad_affine(const float* __restrict__ slots, int rows, float4* __restrict__ affine, float* __restrict__ scales) {
     float m = 0.f;
     for (int k = threadIdx.x; k < RF_AMAX_SLOTS; k += 256) m = fmaxf(m, slots[k]);
-    m = wave_max(m);
-    __shared__ float wm[4];
-    if ((threadIdx.x & 63) == 0) wm[threadIdx.x >> 6] = m;
-    __syncthreads();
-    m = fmaxf(fmaxf(wm[0], wm[1]), fmaxf(wm[2], wm[3]));
+    __shared__ float wm[4][1];
+    rf_waves_put(wm, {wave_max(m)});
+    m = rf_waves_max(wm);
     float s = 1.f;
     if (m > 0.f && m < INFINITY) {
         int e = 9 - ilogbf(m);
@@ -193,7 +189,8 @@ inline int gnb_slices(size_t vol) {                               // >= 4096 ele
 
 // L = lanes per (sample, channel) row = 256 for volumes of >= 1024 elements, else the power of two >= the row's units (16-byte units; elements for
 // 1^3), at least 1: a workgroup takes 256 / L rows (a 4^3 row is 16 units: one row per workgroup left 240 of 256 threads idle -- 0.42 ms for
-// [1024][192][4^3]).  Sums: butterflies inside the row's lanes, then across its waves in order.
+// [1024][192][4^3]).  Sums: butterflies inside the row's lanes, then across its waves in order (a run-time span and a wave range per row: written out
+// here, not wave_sum + rf_waves_sum of lane_reduce.h).
 __global__ __launch_bounds__(256) void k_gnb_partial(const float* __restrict__ x, const float* __restrict__ dxn, size_t vol, int P, int L, int rows,
                                                      double4* __restrict__ part) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -242,6 +239,7 @@ __global__ __launch_bounds__(256) void k_gnb_partial(const float* __restrict__ x
 }
 
 // one 64-thread workgroup per (sample, group); thread k sums the slices of channel k (k, k + 64, ...) in slice order, thread 0 the channels in order
+// (serial sums by one thread, here and in k_gnb_sum_n: none of lane_reduce.h's workgroup reductions)
 __global__ __launch_bounds__(64) void k_gnb_finalize(const double4* __restrict__ part, const float* __restrict__ gamma, int C, int cpg, size_t vol, int P,
                                                      double eps, const float* __restrict__ inv_scale, double2* __restrict__ moments, double4* __restrict__ coef,
                                                      double* __restrict__ a1_out, double* __restrict__ a2_out) {
@@ -479,7 +477,7 @@ __global__ __launch_bounds__(512) void k_conv3_wgrad(WgradArgs a) {
 }
 
 // THE float64 slice-order sum of split-K partials (common.h:rf_slice_sum): out[i] = (float)(parts[i] + parts[count + i] + ... in float64), rounded once.
-// This convolution's, the valid convolution's and the Linear layer's weight gradients end here.  (k_wgrad_split_reduce, conv3d_wgrad_split.hip, is another sum.)
+// This convolution's, the valid convolution's and the Linear layer's weight gradients and the valid convolution's bias gradient end here.  (k_wgrad_split_reduce, conv3d_wgrad_split.hip, is another sum.)
 __global__ __launch_bounds__(256) void k_slice_sum(const float* __restrict__ parts, int slices, size_t count, float* __restrict__ out) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (size_t)gridDim.x * blockDim.x) {
         double s = 0.0;

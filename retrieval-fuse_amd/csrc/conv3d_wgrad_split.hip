@@ -230,7 +230,7 @@ __global__ __launch_bounds__(256) void k_wgrad_split_reduce(const float* __restr
         for (int g = sl; g < gb; g += 4) s += (double)parts[(size_t)g * count + i];
     red[sl][o] = s;
     __syncthreads();
-    if (sl == 0 && i < count) dw[i] = (float)((((red[0][o] + red[1][o]) + red[2][o]) + red[3][o]) * back);
+    if (sl == 0 && i < count) dw[i] = (float)(rf_waves_sum(red, o) * back);
 }
 
 static int wgrad_split_groups(int cin, int cout, int n, int edge) {

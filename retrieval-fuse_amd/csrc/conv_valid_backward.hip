@@ -7,8 +7,8 @@
 #include "common.h"
 
 // ------------------------------------------------------------------------------------------- LeakyReLU backward + db
-// Workgroup (g, co): the flat range [g * chunk, (g + 1) * chunk) of channel co's n * vol elements; its fp32 sum of dz (tree in LDS, fixed order) goes
-// to parts[g][co]; k_db_reduce sums the G partials of a channel in float64.
+// Workgroup (g, co): the flat range [g * chunk, (g + 1) * chunk) of channel co's n * vol elements; its fp32 sum of dz (rf_tree_sum) goes
+// to parts[g][co]; rf_slice_sum adds the G partials of a channel in float64.
 static int lrb_groups(int n, size_t vol) {
     const size_t per = (size_t)n * vol;
     const size_t g = (per + 4095) / 4096;
@@ -17,7 +17,7 @@ static int lrb_groups(int n, size_t vol) {
 
 __global__ __launch_bounds__(256) void k_leaky_bwd(const float* __restrict__ dy, const float* __restrict__ y, int n, int cout, size_t vol, float slope,
                                                    float* __restrict__ dz, float* __restrict__ parts) {
-    __shared__ float red[256];
+    __shared__ float red[256][1];
     const int g = blockIdx.x, G = gridDim.x, co = blockIdx.y, tid = threadIdx.x;
     const size_t per = (size_t)n * vol, chunk = (per + G - 1) / G;
     const size_t j0 = (size_t)g * chunk, j1 = j0 + chunk < per ? j0 + chunk : per;
@@ -30,21 +30,8 @@ __global__ __launch_bounds__(256) void k_leaky_bwd(const float* __restrict__ dy,
         dz[i] = r;
         s += r;
     }
-    red[tid] = s;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if (tid < w) red[tid] += red[tid + w];
-        __syncthreads();
-    }
-    if (tid == 0) parts[(size_t)g * cout + co] = red[0];
-}
-
-__global__ __launch_bounds__(64) void k_db_reduce(const float* __restrict__ parts, int G, int cout, float* __restrict__ db) {
-    const int co = blockIdx.x * 64 + threadIdx.x;
-    if (co >= cout) return;
-    double s = 0.0;
-    for (int g = 0; g < G; ++g) s += (double)parts[(size_t)g * cout + co];
-    db[co] = (float)s;
+    rf_tree_sum(red, {s});
+    if (tid == 0) parts[(size_t)g * cout + co] = red[0][0];
 }
 
 extern "C" size_t rf_conv3d_valid_leaky_backward_ws_bytes(int n, int cout, int so) {
@@ -59,7 +46,7 @@ extern "C" int rf_conv3d_valid_leaky_backward(const float* dy, const float* y, i
     const int G = lrb_groups(n, vol);
     hipStream_t s = (hipStream_t)stream;
     if (int rc = rf_launch<k_leaky_bwd>("rf_conv3d_valid_leaky_backward", dim3(G, cout), dim3(256), s, dy, y, n, cout, vol, slope, dz, (float*)ws)) return rc;
-    return rf_launch<k_db_reduce>("rf_conv3d_valid_leaky_backward(db)", dim3((cout + 63) / 64), dim3(64), s, (const float*)ws, G, cout, db);
+    return rf_slice_sum((const float*)ws, G, (size_t)cout, db, s, "rf_conv3d_valid_leaky_backward(db)");
 }
 
 // --------------------------------------------------------------------------------------------------- data gradient

@@ -56,8 +56,8 @@ template <bool F32>
 __global__ __launch_bounds__(kOccThreads) void k_data_occupancy(const void* __restrict__ store, const long long* __restrict__ offsets, const int* __restrict__ sizes,
                                                                 int n_scenes, const int* __restrict__ items, int w, int pad, float fill, float thr,
                                                                 int* __restrict__ counts) {
-    __shared__ int part[kOccWaves];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, item = blockIdx.x;
+    __shared__ int part[kOccWaves][1];
+    const int item = blockIdx.x;
     const Scene s = scene_of(offsets, sizes, n_scenes, items, item, pad);
     const unsigned w2 = (unsigned)w * w, w3 = w2 * w;
     const bool fill_on = fill <= thr;                 // NaN: unoccupied
@@ -75,14 +75,8 @@ __global__ __launch_bounds__(kOccThreads) void k_data_occupancy(const void* __re
         }
         cnt += __popcll(__ballot(on));
     }
-    if (lane == 0) part[wave] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int total = 0;
-#pragma unroll
-        for (int k = 0; k < kOccWaves; ++k) total += part[k];
-        counts[item] = total;
-    }
+    rf_waves_put(part, {cnt});
+    if (threadIdx.x == 0) counts[item] = rf_waves_sum(part);
 }
 
 template <bool F32, int V>

@@ -37,7 +37,7 @@ size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 __global__ __launch_bounds__(kPackThreads) void k_iou_pack(const void* __restrict__ x, int kind, float scale, float shift, float thr, long long voxels, int words,
                                                            u64* __restrict__ bits, int* __restrict__ counts) {
-    __shared__ int part[kPackWaves];
+    __shared__ int part[kPackWaves][1];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const size_t sample = blockIdx.x;
     const uint8_t* g = reinterpret_cast<const uint8_t*>(x) + sample * (size_t)voxels;
@@ -60,14 +60,8 @@ __global__ __launch_bounds__(kPackThreads) void k_iou_pack(const void* __restric
             cnt += __popcll(m);
         }
     }
-    if (lane == 0) part[wave] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int total = 0;
-#pragma unroll
-        for (int w = 0; w < kPackWaves; ++w) total += part[w];
-        counts[sample] = total;
-    }
+    rf_waves_put(part, {cnt});
+    if (threadIdx.x == 0) counts[sample] = rf_waves_sum(part);
 }
 
 __global__ __launch_bounds__(kThreads) void k_iou_pairs(const u64* __restrict__ bits_a, const int* __restrict__ counts_a, int n_a, const u64* __restrict__ bits_b,

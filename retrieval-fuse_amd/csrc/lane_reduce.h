@@ -1,4 +1,5 @@
-// The FIXED-ORDER reductions of the kernels' epilogues, each defined once: wave reductions, the float64 (sum, sum of squares) butterflies of the GroupNorm
+// The FIXED-ORDER reductions of the kernels' epilogues, each defined once: wave reductions, the workgroup reductions behind them (wave totals in wave order,
+// the maximum over waves, the halving tree), the float64 (sum, sum of squares) butterflies of the GroupNorm
 // statistics, the fused MaxPool3d(2) cell, the recursive-halving transpose sum and the cin = 1 tap loop.  The "bit-equal between routes" tests hold only while
 // every route adds in the same order: a helper here owns the arithmetic and that order; the kernel keeps its barriers, sched_barriers, opaque thread-index
 // copies, LDS addresses and store guards.  Device helpers only, no dependence on the rest of the library (tests/testkit probes them one by one).
@@ -36,6 +37,65 @@ __device__ __forceinline__ double wave_max(double v) {
 // inputs these give the same bits as before.
 __device__ __forceinline__ float rf_max(float a, float b) { return __builtin_elementwise_maximum(a, b); }      // IEEE-754-2019 maximum: v_maximum3_f32
 __device__ __forceinline__ float rf_relu(float v) { return __builtin_elementwise_maximum(v, 0.f); }
+
+// ------------------------------------------------------------------------------------------------------- workgroup reductions
+// The step after a wave of the loss, metric, statistics and backward kernels: wave totals -> a workgroup total.  The kernel owns the __shared__ array and
+// the guard of its store; the helpers own the adds and their order.  "Two calls give the same bits", the float64 kernels that are compared bit for bit
+// with numpy and the loss goldens rest on these orders (tests/test_lane_reduce_gpu.py pins them; profiles/block_reductions_ab.txt).
+//
+// Wave totals through LDS.  rf_waves_put: lane 0 of every wave stores the wave's K wave-uniform values (out of wave_sum / wave_max, or ballot counts) to
+// red[wave][:], then the helper's ONE barrier.  After it ANY thread may take any of the K totals: thread k < K its own (one store each), thread 0 all of
+// them, or every thread.  All NW waves of the workgroup call it.
+template <int NW, int K, class T>
+__device__ __forceinline__ void rf_waves_put(T (&red)[NW][K], const T (&v)[K]) {
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) red[threadIdx.x >> 6][k] = v[k];
+    }
+    __syncthreads();
+}
+// value k's total in WAVE ORDER, left to right from wave 0's own value: ((red[0][k] + red[1][k]) + red[2][k]) + ...  No zero in front: all-(-0.0) wave
+// totals give -0.0, a site that used to start from a literal 0.0 writes `0.0 + rf_waves_sum(..)` to keep its +0.0.  (Also the last step of
+// k_wgrad_split_reduce, whose red[slice][output] holds per-thread sums.)
+template <int NW, int K, class T>
+__device__ __forceinline__ T rf_waves_sum(const T (&red)[NW][K], int k = 0) {
+    static_assert(std::is_same<T, double>::value || std::is_same<T, long long>::value || std::is_same<T, unsigned long long>::value || std::is_same<T, int>::value,
+                  "rf_waves_sum: double, long long, unsigned long long or int");
+    T s = red[0][k];
+#pragma unroll
+    for (int w = 1; w < NW; ++w) s += red[w][k];
+    return s;
+}
+// value k's maximum over the waves, in no promised association.  Safe for the two gradient-maximum kernels it serves: their values are maxima of |x|
+// (>= +0, never -0) and a non-finite gradient was folded into +inf beforehand, so fmaxf (maxNum) meets no NaN to drop and no -0 / +0 pair to order.
+template <int NW, int K>
+__device__ __forceinline__ float rf_waves_max(const float (&red)[NW][K], int k = 0) {
+    float m = red[0][k];
+#pragma unroll
+    for (int w = 1; w < NW; ++w) m = fmaxf(m, red[w][k]);
+    return m;
+}
+// Halving tree over ALL NT threads of the workgroup, K values each: red[t][:] = v, then for o = NT / 2 .. 1 thread t < o does red[t][k] += red[t + o][k],
+// a barrier after the store and after every level.  The totals are red[0][:], valid in thread 0 (whatever a thread added up before -- strided inputs in
+// ascending order at every site -- stays in its kernel).
+template <int NT, int K, class T>
+__device__ __forceinline__ void rf_tree_sum(T (&red)[NT][K], const T (&v)[K]) {
+    static_assert(std::is_same<T, double>::value || std::is_same<T, float>::value, "rf_tree_sum: double or float");
+    static_assert(NT >= 2 && (NT & (NT - 1)) == 0, "the tree halves a power of two");
+    const int t = threadIdx.x;
+#pragma unroll
+    for (int k = 0; k < K; ++k) red[t][k] = v[k];
+    __syncthreads();
+    for (int o = NT / 2; o > 0; o >>= 1) {
+        if (t < o) {
+#pragma unroll
+            for (int k = 0; k < K; ++k) red[t][k] += red[t + o][k];
+        }
+        __syncthreads();
+    }
+}
+// Left as they are, on purpose: k_gnb_partial (run-time butterfly span, per-row wave ranges), k_gnb_finalize / k_gnb_sum_n / k_p2p_finish (one thread's
+// serial sums), k_linear_wgrad (per-lane accumulators summed by wave 0), and every conv forward kernel (the sections below).
 
 // ------------------------------------------------------------------------------------------------------- GroupNorm statistics: accumulators -> sums
 // (sm, sq) += (sum, sum of squares) in float64 of the ReLU'd registers of one accumulator block, in register order ...

@@ -174,7 +174,7 @@ __global__ __launch_bounds__(256) void k_linear_wgrad(const float* __restrict__ 
                 for (int nb = 0; nb < NB; ++nb)
                     acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[u][mb], bv[u][nb], acc[mb][nb], 0, 0, 0);
     }
-    // D rows 4*kq + r (m), column li (n): waves 1..3 -> LDS, wave 0 adds them in wave order
+    // D rows 4*kq + r (m), column li (n): waves 1..3 -> LDS, wave 0 adds them in wave order (per-lane accumulators, wave 0's stay in registers: not rf_waves_sum)
     if (wave > 0) {
 #pragma unroll
         for (int mb = 0; mb < MB; ++mb)

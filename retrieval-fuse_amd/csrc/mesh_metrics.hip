@@ -221,18 +221,14 @@ __global__ __launch_bounds__(256) void k_p2p_stats(const double* __restrict__ d2
             else atomicAdd(&counts[lo], 1ull);
         }
     }
-    s_dist = wave_sum(s_dist);
-    s_d2 = wave_sum(s_d2);
-    s_dot = wave_sum(s_dot);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][0] = s_dist, red[threadIdx.x >> 6][1] = s_d2, red[threadIdx.x >> 6][2] = s_dot;
-    __syncthreads();
-    if (threadIdx.x < 3) partial[3 * blockIdx.x + threadIdx.x] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
+    rf_waves_put(red, {wave_sum(s_dist), wave_sum(s_d2), wave_sum(s_dot)});
+    if (threadIdx.x < 3) partial[3 * blockIdx.x + threadIdx.x] = rf_waves_sum(red, threadIdx.x);
     if (lds_hist)
         for (int t = threadIdx.x; t < n_thr; t += blockDim.x)
             if (hist[t]) atomicAdd(&counts[t], (unsigned long long)hist[t]);
 }
 
-// one workgroup: sums[k] = the partial sums added in slot order; counts: histogram -> inclusive prefix sums
+// one workgroup: sums[k] = the partial sums added in slot order (one thread's serial sum, numpy's order: no rf_tree_sum); counts: histogram -> inclusive prefix sums
 __global__ __launch_bounds__(256) void k_p2p_finish(const double* __restrict__ partial, int n_partial, unsigned long long* __restrict__ counts, int n_thr,
                                                     double* __restrict__ sums) {
     __shared__ unsigned long long chunk_sum[256];

@@ -83,15 +83,9 @@ __global__ __launch_bounds__(256) void k_occ_pack(const void* __restrict__ pred,
             ni += __popcll(bp & bt);
         }
     }
-    if (lane == 0) {
-        part[wave][0] = np;
-        part[wave][1] = nt;
-        part[wave][2] = ni;
-    }
-    __syncthreads();
+    rf_waves_put(part, {np, nt, ni});                                  // ballot counts: wave-uniform already
     if (threadIdx.x < 3) {
-        unsigned long long s = 0;
-        for (int r = 0; r < kRows; ++r) s += part[r][threadIdx.x];
+        const unsigned long long s = rf_waves_sum(part, threadIdx.x);
         if (s) atomicAdd(reinterpret_cast<unsigned long long*>(out + plane / D * 5 + threadIdx.x), s);
     }
 }
@@ -104,7 +98,7 @@ template <bool FIRST>
 __global__ __launch_bounds__(256) void k_minplus(int B, int D, int H, int W, const unsigned long long* __restrict__ bits_p,
                                                  const unsigned long long* __restrict__ bits_t, int* __restrict__ g2, long long* __restrict__ out) {
     __shared__ int u[kTile][kTile];
-    __shared__ long long part[kRows];
+    __shared__ long long part[kRows][1];
     const int A = FIRST ? H : D;
     const long long X = FIRST ? (long long)W : (long long)H * W;
     const long long tiles_a = (A + kTile - 1) / kTile;
@@ -176,12 +170,9 @@ __global__ __launch_bounds__(256) void k_minplus(int B, int D, int H, int W, con
         const int v = min(best[j] + a * a, kInf);
         if (((qmask >> j) & 1u) && v < kInf) s += v;                   // an empty source grid leaves every value at kInf: its sum stays 0
     }
-    s = wave_sum(s);
-    if (tx == 0) part[r] = s;
-    __syncthreads();
+    rf_waves_put(part, {wave_sum(s)});
     if (threadIdx.x == 0) {
-        long long t = 0;
-        for (int i = 0; i < kRows; ++i) t += part[i];
+        const long long t = rf_waves_sum(part);
         if (t) atomicAdd(reinterpret_cast<unsigned long long*>(out + b * 5 + 3 + dir), (unsigned long long)t);
     }
 }

@@ -230,17 +230,12 @@ __global__ __launch_bounds__(kThreads) void k_ntx_lse(const float* __restrict__ 
 
 // one workgroup: thread k adds the terms of compact slots k, k + 256, ... (zjs then zis of each), then a fixed tree over the 256 threads
 __global__ __launch_bounds__(kThreads) void k_ntx_finish(const int* __restrict__ hdr, const double* __restrict__ term, int max_rows, float* __restrict__ loss) {
-    __shared__ double red[kThreads];
+    __shared__ double red[kThreads][1];
     const int taken = hdr[1];
     double acc = 0.0;
     for (int c = threadIdx.x; c < taken; c += kThreads) acc += term[c] + term[max_rows + c];
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int s = kThreads / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) loss[0] = (float)red[0];
+    rf_tree_sum(red, {acc});
+    if (threadIdx.x == 0) loss[0] = (float)red[0][0];
 }
 
 __global__ __launch_bounds__(kThreads) void k_ntx_bwd(const float* __restrict__ iou, const float* __restrict__ grad_loss, const int* __restrict__ hdr,

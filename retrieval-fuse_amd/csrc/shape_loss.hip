@@ -157,17 +157,8 @@ __global__ __launch_bounds__(kThreads) void k_shape_loss(const float* __restrict
             }
         }
     }
-    sum_l1 = wave_sum(sum_l1);
-    sum_cos = wave_sum(sum_cos);
-    n_valid = wave_sum(n_valid);
-    n_both = wave_sum(n_both);
-    if ((threadIdx.x & 63) == 0) {
-        double* r = red[threadIdx.x >> 6];
-        r[0] = sum_l1, r[1] = sum_cos, r[2] = n_valid, r[3] = n_both;
-    }
-    __syncthreads();
-    if (threadIdx.x < kPartials)
-        partial[(size_t)blockIdx.x * kPartials + threadIdx.x] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
+    rf_waves_put(red, {wave_sum(sum_l1), wave_sum(sum_cos), wave_sum(n_valid), wave_sum(n_both)});
+    if (threadIdx.x < kPartials) partial[(size_t)blockIdx.x * kPartials + threadIdx.x] = rf_waves_sum(red, threadIdx.x);
 }
 
 // one workgroup: thread k adds the partials of workgroups k, k + 256, ... in ascending order, then a fixed tree over the 256 threads
@@ -178,15 +169,7 @@ __global__ __launch_bounds__(256) void k_shape_loss_finish(const double* __restr
     for (int b = threadIdx.x; b < n_partial; b += 256)
 #pragma unroll
         for (int k = 0; k < kPartials; ++k) acc[k] += partial[(size_t)b * kPartials + k];
-#pragma unroll
-    for (int k = 0; k < kPartials; ++k) red[threadIdx.x][k] = acc[k];
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o)
-#pragma unroll
-            for (int k = 0; k < kPartials; ++k) red[threadIdx.x][k] += red[threadIdx.x + o][k];
-        __syncthreads();
-    }
+    rf_tree_sum(red, acc);
     if (threadIdx.x == 0) {
         const float l1 = do_l1 ? (float)(red[0][0] / n_voxels) : 0.f;
         const float normal = do_normal ? 1.f - (float)(red[0][1] / red[0][2]) : 0.f;      // no valid voxel: 0 / 0 = NaN, as the reference's mean of nothing

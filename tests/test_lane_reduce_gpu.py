@@ -6,6 +6,8 @@ that order at its source.  One wave (tests/testkit: rft_lane_reduce_probe) calls
   * float64 values whose sum depends on the order (magnitude 2^20, random signs and mantissas: every add of every level rounds) -- compared bit
     for bit with a numpy emulation that adds in the documented partner order.  That the inputs tell that order from its neighbours (a swapped
     pair of masks, at the start or at the end of the tree) is asserted on the emulation itself.
+The workgroup reductions (wave totals in wave order, the maximum over waves, the halving tree) get the same treatment on 32 workgroups of 256 threads
+(rft_block_reduce_probe), at the end of this file: which thread holds what, the order of the adds against its neighbours, and the sign of a zero sum.
 """
 import numpy as np
 import pytest
@@ -143,3 +145,108 @@ def test_order_sensitive_values_pin_the_partner_order(gpu):
         sm, sq = sm + t, sq + t * t
     assert np.array_equal(dout[:, 9], sm, equal_nan=True) and np.isnan(dout[5, 9]) and np.isnan(dout[:, 9]).sum() == 1
     assert np.array_equal(dout[:, 10], sq, equal_nan=True)
+
+
+# ------------------------------------------------------------------------------------------------------- workgroup reductions
+# 32 workgroups x 256 threads (tests/testkit: rft_block_reduce_probe); the emulations below work on [32 workgroups][256 threads][columns].
+WG, NT = 32, 256
+
+
+def wave_totals(x):
+    """x [32, 256, K] -> [32, 4, K]: wave_sum's total of every wave, as lane 0 holds it (partner masks 32, 16, .. 1, the order of wave_sum's loop)."""
+    w = x.reshape(WG, 4, 64, -1).transpose(2, 0, 1, 3)                   # lanes first, for xor_sum
+    return xor_sum(w, (32, 16, 8, 4, 2, 1))[0]
+
+
+def waves_sum(r):
+    """r [32, 4, K] -> [32, K]: ((r0 + r1) + r2) + r3, from wave 0's own value."""
+    return ((r[:, 0] + r[:, 1]) + r[:, 2]) + r[:, 3]
+
+
+def tree_sum(x):
+    """x [32, 256, K] -> [32, K]: red[t] += red[t + o] for o = 128 .. 1."""
+    x = x.copy()
+    o = NT // 2
+    while o > 0:
+        x[:, :o] = x[:, :o] + x[:, o:2 * o]
+        o //= 2
+    return x[:, 0]
+
+
+def serial_sum(x):
+    """x [32, 256, K] -> [32, K]: one thread adding in thread order, from thread 0's own value."""
+    s = x[:, 0].copy()
+    for t in range(1, NT):
+        s = s + x[:, t]
+    return s
+
+
+def block_inputs(dseed, fseed):
+    rng = np.random.default_rng(dseed)
+    din = rng.standard_normal((WG, NT, 5)) * 2.0 ** 20                   # order_sensitive()'s values, per (workgroup, thread, column)
+    frng = np.random.default_rng(fseed)
+    fin = np.stack([frng.standard_normal((WG, NT)) * 2.0 ** 20, np.abs(frng.standard_normal((WG, NT)))], axis=2).astype(np.float32)
+    lin = frng.integers(-2 ** 40, 2 ** 40, size=(WG, NT))
+    return din, fin, lin
+
+
+def run_block_probe(din, fin, lin):
+    dout, fout, lout = testkit.block_reduce_probe(torch.from_numpy(din).cuda(), torch.from_numpy(fin).cuda(), torch.from_numpy(lin).cuda())
+    torch.cuda.synchronize()
+    return dout.cpu().numpy(), fout.cpu().numpy(), lout.cpu().numpy()
+
+
+def test_block_small_integers_say_which_thread_holds_what(gpu):
+    rng = np.random.default_rng(21)
+    din = rng.integers(-9, 10, size=(WG, NT, 5)).astype(np.float64)
+    fin = rng.integers(0, 1000, size=(WG, NT, 2)).astype(np.float32)
+    fin[..., 0] -= 500
+    lin = rng.integers(-9, 10, size=(WG, NT))
+    dout, fout, lout = run_block_probe(din, fin, lin)
+    total = din.sum(axis=1)                                              # every one of the 256 inputs counted once, whatever the order
+    assert np.array_equal(dout[:, 0], total)                             # wave-order sum: thread k < K holds value k (K = 1: column 0, K = 4: columns 1 .. 4)
+    assert np.array_equal(dout[:, 1], total)                             # ... and any thread may read all of them after the barrier (here the last one)
+    assert np.array_equal(dout[:, 2], total)                             # 0.0 + the sum
+    assert np.array_equal(dout[:, 3], total)                             # halving tree: thread 0
+    assert np.array_equal(fout[:, 0], fin[..., 0].sum(axis=1, dtype=np.float64).astype(np.float32))     # |sum| < 2^24: exact in float32
+    assert np.array_equal(fout[:, 1], fin[..., 1].max(axis=1)) and np.array_equal(fout[:, 2], fout[:, 1])
+    assert np.array_equal(lout[:, 0], lin.sum(axis=1)) and np.array_equal(lout[:, 1], lout[:, 0])
+
+
+def test_block_order_sensitive_values_pin_the_order(gpu):
+    din, fin, lin = block_inputs(31, 32)
+    r = wave_totals(din)
+    want_waves, want_tree = waves_sum(r), tree_sum(din)
+    # the inputs tell each order from its neighbours (numpy against numpy), on the K = 4 columns: 32 workgroups x 4 values = 128 results
+    k4 = slice(1, 5)
+    right_to_left = ((r[:, 3] + r[:, 2]) + r[:, 1]) + r[:, 0]
+    pairs = (r[:, 0] + r[:, 1]) + (r[:, 2] + r[:, 3])
+    up_masks = waves_sum(xor_sum(din.reshape(WG, 4, 64, -1).transpose(2, 0, 1, 3), (1, 2, 4, 8, 16, 32))[0])      # wave_sum with its masks the other way round
+    for name, other in (('right to left', right_to_left), ('pairs', pairs), ('masks 1 .. 32', up_masks)):
+        assert want_waves[:, k4].size == 128 and differing(want_waves[:, k4], other[:, k4]) >= 16, name
+    for name, other in (('serial', serial_sum(din)), ('wave first', want_waves)):
+        assert differing(want_tree[:, k4], other[:, k4]) >= 16, name
+    f0 = fin[..., :1]
+    want_ftree = tree_sum(f0)
+    assert want_ftree.dtype == np.float32 and differing(want_ftree, serial_sum(f0)) >= 8         # 32 results here
+    dout, fout, lout = run_block_probe(din, fin, lin)
+    assert same_bits(dout[:, 0], want_waves)
+    assert same_bits(dout[:, 1], want_waves)
+    assert same_bits(dout[:, 2], 0.0 + want_waves)
+    assert same_bits(dout[:, 3], want_tree)
+    assert same_bits(fout[:, 0], want_ftree[:, 0])
+    assert np.array_equal(fout[:, 1], fin[..., 1].max(axis=1)) and np.array_equal(fout[:, 2], fout[:, 1])
+    assert np.array_equal(lout[:, 0], lin.sum(axis=1)) and np.array_equal(lout[:, 1], lout[:, 0])
+
+
+def test_block_sign_of_zero(gpu):
+    """All-(-0.0) inputs: the wave-order sum starts from wave 0's own value and gives -0.0; `0.0 +` it gives the +0.0 that k_gn_partial's sum from a
+    literal 0.0 produced (rf_gn_stats keeps writing it that way).  The tree has no zero in front either."""
+    din = np.full((WG, NT, 5), -0.0)
+    fin = np.zeros((WG, NT, 2), np.float32)
+    fin[..., 0] = -0.0
+    dout, fout, lout = run_block_probe(din, fin, np.zeros((WG, NT), np.int64))
+    assert (dout == 0).all() and (fout == 0).all() and (lout == 0).all()
+    assert np.signbit(dout[:, 0]).all() and np.signbit(dout[:, 1]).all()
+    assert not np.signbit(dout[:, 2]).any()
+    assert np.signbit(dout[:, 3]).all() and np.signbit(fout[:, 0]).all()

@@ -19,6 +19,7 @@ def load():
         _lib.rft_poison_vgprs.argtypes = [ctypes.c_void_p]
         _lib.rft_f16_mfma_load.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
         _lib.rft_lane_reduce_probe.argtypes = [ctypes.c_void_p] * 6
+        _lib.rft_block_reduce_probe.argtypes = [ctypes.c_void_p] * 7
     return _lib
 
 
@@ -42,3 +43,19 @@ def lane_reduce_probe(din, fin):
     if rc != 0:
         raise RuntimeError('rft_lane_reduce_probe: HIP error %d' % rc)
     return dout, fout, iout
+
+
+def block_reduce_probe(din, fin, lin):
+    """32 workgroups x 256 threads run the workgroup reductions of csrc/lane_reduce.h: din [32, 256, 5] float64, fin [32, 256, 2] float32 and
+    lin [32, 256] int64 on the GPU -> (dout [32, 4, 5], fout [32, 3], lout [32, 2]); the rows and columns are described at k_block_reduce_probe."""
+    assert din.shape == (32, 256, 5) and din.dtype == torch.float64 and din.is_contiguous() and din.is_cuda
+    assert fin.shape == (32, 256, 2) and fin.dtype == torch.float32 and fin.is_contiguous() and fin.is_cuda
+    assert lin.shape == (32, 256) and lin.dtype == torch.int64 and lin.is_contiguous() and lin.is_cuda
+    dout = torch.empty(32, 4, 5, dtype=torch.float64, device=din.device)
+    fout = torch.empty(32, 3, dtype=torch.float32, device=din.device)
+    lout = torch.empty(32, 2, dtype=torch.int64, device=din.device)
+    rc = load().rft_block_reduce_probe(din.data_ptr(), fin.data_ptr(), lin.data_ptr(), dout.data_ptr(), fout.data_ptr(), lout.data_ptr(),
+                                       torch.cuda.current_stream().cuda_stream)
+    if rc != 0:
+        raise RuntimeError('rft_block_reduce_probe: HIP error %d' % rc)
+    return dout, fout, lout

@@ -6,6 +6,7 @@
 //                                       lanes 48..63 (DESIGN 4.7); tests/test_two_stream_gpu.py runs every kernel family of the library beside it.
 //   rft_lane_reduce_probe             : one wave calls every fixed-order reduction of csrc/lane_reduce.h on per-lane inputs and stores every lane's
 //                                       result (tests/test_lane_reduce_gpu.py pins which lane gets which value, and the order of the adds)
+//   rft_block_reduce_probe            : 32 workgroups call the workgroup reductions of that header (wave-order sum, maximum over waves, halving tree)
 #include <hip/hip_runtime.h>
 #include "../../retrieval-fuse_amd/csrc/lane_reduce.h"      // f32x4 and the helpers under test
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
@@ -95,5 +96,56 @@ __global__ __launch_bounds__(64) void k_lane_reduce_probe(const double* __restri
 
 extern "C" int rft_lane_reduce_probe(const double* din, const float* fin, double* dout, float* fout, int* iout, void* stream) {
     hipLaunchKernelGGL(k_lane_reduce_probe, dim3(1), dim3(64), 0, (hipStream_t)stream, din, fin, dout, fout, iout);
+    return (int)hipGetLastError();
+}
+
+// The workgroup reductions: 32 workgroups x 256 threads, each workgroup on its own inputs.  din [32][256][5]: column 0 = the K = 1 value, 1 .. 4 = the K = 4
+// values; fin [32][256][2]: the float tree's value, the (non-negative) value of the maximum; lin [32][256]: the integer sum's value.
+// dout [32][4][5]: the wave-order sums as thread k < K holds them (K = 1: thread 0) | all of them as the LAST thread reads them | 0.0 + the sums (thread 0) |
+// the halving tree's red[0][:] in thread 0.  fout [32][3]: the float tree, the maximum in thread 0, in the last thread.  lout [32][2]: thread 0, last thread.
+__global__ __launch_bounds__(256) void k_block_reduce_probe(const double* __restrict__ din, const float* __restrict__ fin, const long long* __restrict__ lin,
+                                                            double* __restrict__ dout, float* __restrict__ fout, long long* __restrict__ lout) {
+    __shared__ double w1[4][1], w4[4][4], t1[256][1], t4[256][4];
+    __shared__ float tf[256][1], wm[4][1];
+    __shared__ long long wl[4][1];
+    const int t = threadIdx.x, b = blockIdx.x;
+    const size_t e = (size_t)b * 256 + t;
+    const double d1[1] = {din[e * 5]}, d4[4] = {din[e * 5 + 1], din[e * 5 + 2], din[e * 5 + 3], din[e * 5 + 4]};
+    double* o = dout + (size_t)b * 20;
+    rf_waves_put(w1, {wave_sum(d1[0])});
+    rf_waves_put(w4, {wave_sum(d4[0]), wave_sum(d4[1]), wave_sum(d4[2]), wave_sum(d4[3])});
+    rf_waves_put(wm, {wave_max(fin[e * 2 + 1])});
+    rf_waves_put(wl, {wave_sum(lin[e])});
+    if (t == 0) o[0] = rf_waves_sum(w1);
+    if (t < 4) o[1 + t] = rf_waves_sum(w4, t);
+    if (t == 255) {
+        o[5] = rf_waves_sum(w1);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) o[6 + k] = rf_waves_sum(w4, k);
+    }
+    if (t == 0) {
+        o[10] = 0.0 + rf_waves_sum(w1);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) o[11 + k] = 0.0 + rf_waves_sum(w4, k);
+        fout[b * 3 + 1] = rf_waves_max(wm);
+        lout[b * 2] = rf_waves_sum(wl);
+    }
+    if (t == 255) {
+        fout[b * 3 + 2] = rf_waves_max(wm);
+        lout[b * 2 + 1] = rf_waves_sum(wl);
+    }
+    rf_tree_sum(t1, d1);
+    rf_tree_sum(t4, d4);
+    rf_tree_sum(tf, {fin[e * 2]});
+    if (t == 0) {
+        o[15] = t1[0][0];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) o[16 + k] = t4[0][k];
+        fout[b * 3] = tf[0][0];
+    }
+}
+
+extern "C" int rft_block_reduce_probe(const double* din, const float* fin, const long long* lin, double* dout, float* fout, long long* lout, void* stream) {
+    hipLaunchKernelGGL(k_block_reduce_probe, dim3(32), dim3(256), 0, (hipStream_t)stream, din, fin, lin, dout, fout, lout);
     return (int)hipGetLastError();
 }
