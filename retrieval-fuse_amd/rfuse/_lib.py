@@ -1,6 +1,7 @@
 """ctypes binding of librfuse_hip.so (the C ABI declared in include/rfuse.h, the evaluation ABI of include/rfuse_eval.h, the training-loss ABI
 of include/rfuse_train.h, the contrastive-loss ABI of include/rfuse_contrastive.h, the pairwise-occupancy ABI of include/rfuse_pairs.h, the
-attention-backward ABI of include/rfuse_attn_train.h, the level ABI of include/rfuse_level.h and the dataset ABI of include/rfuse_data.h).
+attention-backward ABI of include/rfuse_attn_train.h, the level ABI of include/rfuse_level.h, the dataset ABI of include/rfuse_data.h and the
+optimiser ABI of include/rfuse_optim.h).
 
 The argument and return types are read from the header itself at import (``parse_header``): there is no second copy of the ABI to keep
 in step.  There is NO fallback: if the library is missing a RuntimeError is raised, and every entry point that returns a status
@@ -13,7 +14,8 @@ rfuse/losses.py) and ``load_contrastive()`` include/rfuse_contrastive.h (``CONTR
 loss, rfuse/losses.py) and ``load_pairs()`` include/rfuse_pairs.h (``PAIRS_SIGNATURES``: the retrieval trainer's IoU matrix, rfuse/losses.py) and ``load_attn_train()`` include/rfuse_attn_train.h
 (``ATTN_TRAIN_SIGNATURES``: the backward of the patch attention's row route, rfuse/ops.py) and ``load_level()`` include/rfuse_level.h (``LEVEL_SIGNATURES``:
 a whole encoder level in one launch, rfuse/ops.py) and ``load_data()`` include/rfuse_data.h (``DATA_SIGNATURES``: the patch dataset's occupancy counts and batch
-windows, rfuse/data.py), all from the same shared object, under the same status rule.
+windows, rfuse/data.py) and ``load_optim()`` the ninth header include/rfuse_optim.h (``OPTIM_SIGNATURES``: the multi-tensor Adam step, rfuse/optim.py), all from the
+same shared object, under the same status rule.
 """
 import ctypes
 import os
@@ -32,6 +34,7 @@ PAIRS_HEADER_PATH = _HERE.parents[1] / 'include' / 'rfuse_pairs.h'
 ATTN_TRAIN_HEADER_PATH = _HERE.parents[1] / 'include' / 'rfuse_attn_train.h'
 LEVEL_HEADER_PATH = _HERE.parents[1] / 'include' / 'rfuse_level.h'
 DATA_HEADER_PATH = _HERE.parents[1] / 'include' / 'rfuse_data.h'
+OPTIM_HEADER_PATH = _HERE.parents[1] / 'include' / 'rfuse_optim.h'
 
 # every scalar type include/rfuse.h uses; any pointer is a c_void_p, and `const char*` as a return type a c_char_p
 _SCALARS = {'int': ctypes.c_int, 'float': ctypes.c_float, 'size_t': ctypes.c_size_t, 'int64_t': ctypes.c_int64, 'long long': ctypes.c_int64}
@@ -86,6 +89,7 @@ PAIRS_SIGNATURES = parse_header(PAIRS_HEADER_PATH.read_text())
 ATTN_TRAIN_SIGNATURES = parse_header(ATTN_TRAIN_HEADER_PATH.read_text())
 LEVEL_SIGNATURES = parse_header(LEVEL_HEADER_PATH.read_text())
 DATA_SIGNATURES = parse_header(DATA_HEADER_PATH.read_text())
+OPTIM_SIGNATURES = parse_header(OPTIM_HEADER_PATH.read_text())
 
 
 def is_status(name, table=None):
@@ -108,6 +112,7 @@ _pairs = None
 _attn_train = None
 _level = None
 _data = None
+_optim = None
 
 
 class _Library:
@@ -217,6 +222,14 @@ def load_data():
     if _data is None:
         _data = _Library(load()._cdll, DATA_SIGNATURES)
     return _data
+
+
+def load_optim():
+    """The entry points of include/rfuse_optim.h, bound like ``load_eval()``'s."""
+    global _optim
+    if _optim is None:
+        _optim = _Library(load()._cdll, OPTIM_SIGNATURES)
+    return _optim
 
 
 def check(rc, what):

@@ -37,6 +37,10 @@ through the drop-in modules in grad mode; loss and every parameter gradient are 
 tests/test_autograd_gpu.py.  Not built: backward of the pre-split pair routes and the fused attention MLP (grad mode takes the plain routes), the
 BatchNorm patch encoders (PatchNorm08 / PatchNorm32: no shipped config selects them) and the patch encoders' forward_grid (the database build and
 the queries never train).
+
+What follows the backward -- the parameter update -- is HIP too: ``rfuse.optim.Adam`` (rfuse/optim.py over csrc/optim.hip, declared in a ninth header,
+include/rfuse_optim.h) is torch.optim.Adam's update in one pass over all parameters; it bumps the parameters' version counters like torch's in-place
+update, so the images and range decisions the layers above derive from their weights follow it.
 """
 import torch
 import torch.nn.functional as F

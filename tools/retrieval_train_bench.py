@@ -46,12 +46,16 @@ def conv_flops(net, b, win):
     return fwd, bwd
 
 
-def run(pair, steps, warmup):
+def run(pair, steps, warmup, optimizer='torch'):
     (qn, qnf, qw), (tn, tnf, tw), b = PAIRS[pair]
     dev = torch.device('cuda:0')
     torch.manual_seed(0)
     fq, ft = getattr(retrieval, qn)(qnf, 64).to(dev), getattr(retrieval, tn)(tnf, 64).to(dev)
-    opt = torch.optim.Adam(list(fq.parameters()) + list(ft.parameters()), lr=1e-4, weight_decay=5e-5)
+    if optimizer == 'rfuse':
+        from rfuse.optim import Adam
+    else:
+        Adam = torch.optim.Adam
+    opt = Adam(list(fq.parameters()) + list(ft.parameters()), lr=1e-4, weight_decay=5e-5)
     loss_mod = NTXentLoss(0.2, True)
     g = torch.Generator().manual_seed(1)
     xq = (torch.rand(b, 1, qw, qw, qw, generator=g) * 2 - 1).to(dev)
@@ -100,7 +104,7 @@ def run(pair, steps, warmup):
     fwd, bwd = sum(f for f, _ in fl), sum(x for _, x in fl)
     new_ms = sum(table[k][1] for k in NEW_KERNELS)
     kern_ms = sum(v[1] for v in table.values())
-    out = {'pair': pair, 'batch': b, 'encoders': [qn, tn], 'ms_per_step': round(ms, 3), 'fwd_gflop': round(fwd / 1e9, 2), 'bwd_gflop': round(bwd / 1e9, 2),
+    out = {'pair': pair, 'batch': b, 'encoders': [qn, tn], 'optimizer': optimizer, 'ms_per_step': round(ms, 3), 'fwd_gflop': round(fwd / 1e9, 2), 'bwd_gflop': round(bwd / 1e9, 2),
            'tflops_step': round((fwd + bwd) / ms / 1e9, 2), 'profiled_kernel_ms': round(kern_ms, 3), 'new_kernels_ms': round(new_ms, 3),
            'new_kernels_share_of_step': round(new_ms / ms, 3)}
     layer_flop = 2 * 128 * 24 * 12 * 27 * 42 ** 3
@@ -119,9 +123,10 @@ def main():
     ap.add_argument('--steps', type=int, default=10)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--out', default=None, help='directory for retrieval_train_<pair>.txt')
+    ap.add_argument('--optimizer', choices=['torch', 'rfuse'], default='torch', help='rfuse: the update by rfuse.optim.Adam (csrc/optim.hip); the committed profiles use torch')
     a = ap.parse_args()
     for pair in a.pairs:
-        res, table = run(pair, a.steps, a.warmup)
+        res, table = run(pair, a.steps, a.warmup, a.optimizer)
         print(table)
         print(json.dumps(res), flush=True)
         if a.out:

@@ -2,8 +2,11 @@
 forward_full -> L1 on df -> backward through all four networks, Adam step) through the drop-in modules in grad mode, timed with HIP
 events, next to the same step of the oracle on the host CPU (torch fp32 autograd).  Prints one JSON line.
 
-    python tools/train_bench.py [config] [batch] [steps]
+    python tools/train_bench.py [config] [batch] [steps] [--optimizer torch|rfuse] [--no-cpu-oracle]
+
+--optimizer rfuse: the parameter update by rfuse.optim.Adam (csrc/optim.hip) instead of torch.optim.Adam; the default stays torch, the committed profiles'.
 """
+import argparse
 import contextlib
 import io
 import json
@@ -19,9 +22,14 @@ import model
 from model.attention import Fold3D, Unfold3D
 from rfuse import _lib, configs as rf_configs
 
-name = sys.argv[1] if len(sys.argv) > 1 else 'C3'
-B = int(sys.argv[2]) if len(sys.argv) > 2 else 4
-steps = int(sys.argv[3]) if len(sys.argv) > 3 else 5
+ap = argparse.ArgumentParser()
+ap.add_argument('config', nargs='?', default='C3')
+ap.add_argument('batch', nargs='?', type=int, default=4)
+ap.add_argument('steps', nargs='?', type=int, default=5)
+ap.add_argument('--optimizer', choices=['torch', 'rfuse'], default='torch', help='rfuse: the update by rfuse.optim.Adam (csrc/optim.hip); the committed profiles use torch')
+ap.add_argument('--no-cpu-oracle', action='store_true', help="leave out the oracle's step on the host CPU (tools/optim_bench.py runs this tool many times)")
+args = ap.parse_args()
+name, B, steps, optimizer, cpu_oracle = args.config, args.batch, args.steps, args.optimizer, not args.no_cpu_oracle
 cfg = rf_configs.get_config(name)
 _, trunc_t = rf_configs.truncations(cfg)
 K, S = cfg['K'], cfg['dataset_train']['input_chunk_size'] if 'dataset_train' in cfg and 'input_chunk_size' in cfg['dataset_train'] else 8
@@ -33,7 +41,11 @@ with contextlib.redirect_stdout(io.StringIO()):
 for m in mods.values():
     m.to(dev).train()
 params = [p for m in mods.values() for p in m.parameters()]
-opt = torch.optim.Adam(params, lr=1e-4)
+if optimizer == 'rfuse':
+    from rfuse.optim import Adam
+    opt = Adam(params, lr=1e-4)
+else:
+    opt = torch.optim.Adam(params, lr=1e-4)
 gen = torch.Generator().manual_seed(3)
 x_in = torch.randn(B, 1, S, S, S, generator=gen).to(dev)
 retr = torch.randn(B, K, 64, 64, 64, generator=gen).to(dev)
@@ -76,6 +88,13 @@ for entry, _, a0, a1, _nulls in records:
     agg[entry] = agg.get(entry, 0.0) + a0.elapsed_time(a1)
 top = sorted(agg.items(), key=lambda kv: -kv[1])[:8]
 
+result = {'metric': 'training steps/s (forward_full + backward + Adam, phase 3: all four networks trainable)', 'config': name, 'chunks_per_step': B,
+          'optimizer': optimizer, 'ms_per_step': ms, 'chunks_per_s': B / ms * 1e3, 'loss': float(loss),
+          'hip_entry_points_ms': {k: round(v, 3) for k, v in top}, 'hip_ms_total': round(sum(agg.values()), 3)}
+if not cpu_oracle:
+    print(json.dumps(result))
+    sys.exit(0)
+
 # the oracle's step on the host CPU (fp32 autograd), bounded sample
 from oracle import refpath
 sds = {k: {n: v.detach().cpu().clone().requires_grad_(True) for n, v in m.state_dict().items() if v.dtype.is_floating_point} for k, m in mods.items()}
@@ -86,7 +105,5 @@ noise_c = (-torch.empty(bc * 4096, K).exponential_().log()) if cfg['attn_retriev
 dfo = refpath.forward_full(sds, cfg, x_in[:bc].cpu(), retr[:bc].cpu(), trunc_t, noise_c)
 (dfo - target[:bc].cpu()).abs().mean().backward()
 cpu_s = time.time() - t0
-print(json.dumps({'metric': 'training steps/s (forward_full + backward + Adam, phase 3: all four networks trainable)', 'config': name, 'chunks_per_step': B,
-                  'ms_per_step': ms, 'chunks_per_s': B / ms * 1e3, 'loss': float(loss),
-                  'hip_entry_points_ms': {k: round(v, 3) for k, v in top}, 'hip_ms_total': round(sum(agg.values()), 3),
-                  'cpu_oracle': {'chunks_per_s': bc / cpu_s, 'threads': torch.get_num_threads(), 'sample': '%d chunks, fp32 torch autograd of oracle/refpath.py' % bc}}))
+result['cpu_oracle'] = {'chunks_per_s': bc / cpu_s, 'threads': torch.get_num_threads(), 'sample': '%d chunks, fp32 torch autograd of oracle/refpath.py' % bc}
+print(json.dumps(result))
