@@ -8,7 +8,7 @@ from pathlib import Path
 
 HERE = Path(__file__).resolve().parent
 OUT = HERE.parent / 'rfuse' / 'librfuse_hip.so'
-SOURCES = ['capi.hip', 'conv3d.hip', 'conv3d_mfma.hip', 'conv3d_up.hip', 'conv3d_up_split.hip', 'conv3d_split.hip', 'conv3d_split_zc.hip', 'conv3d_e2_split.hip', 'conv3d_e2_level.hip', 'conv3d_small.hip', 'conv3d_backward.hip', 'conv3d_wgrad_split.hip', 'conv_valid_mfma.hip', 'conv_valid_split.hip', 'conv_valid_split_pg.hip', 'conv_valid_backward.hip', 'linear.hip', 'attention.hip', 'attention_backward.hip', 'attention_fused.hip', 'retrieval.hip', 'mesh.hip', 'metrics.hip', 'mesh_metrics.hip', 'shape_loss.hip', 'ntxent.hip', 'iou_matrix.hip', 'optim.hip', 'dataset.hip']
+SOURCES = ['capi.hip', 'conv3d.hip', 'conv3d_mfma.hip', 'conv3d_up.hip', 'conv3d_up_split.hip', 'conv3d_split.hip', 'conv3d_split_zc.hip', 'conv3d_e2_split.hip', 'conv3d_e2_level.hip', 'conv3d_small.hip', 'conv3d_backward.hip', 'conv3d_wgrad_split.hip', 'conv_valid_mfma.hip', 'conv_valid_split.hip', 'conv_valid_split_pg.hip', 'conv_valid_backward.hip', 'linear.hip', 'attention.hip', 'attention_backward.hip', 'attention_fused.hip', 'retrieval.hip', 'mesh.hip', 'metrics.hip', 'mesh_metrics.hip', 'shape_loss.hip', 'ntxent.hip', 'iou_matrix.hip', 'refinement_step.hip', 'optim.hip', 'dataset.hip']
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wall', '-Wno-unused-function']
 # the attention / gather-normalise kernels restate torch expressions op by op: no a*b+c fusion across operations (explicit fmaf() stays an FMA).
 # hipcc's default -ffp-contract=fast fuses in the backend, where neither __fmul_rn nor `#pragma clang fp contract(off)` reach.
@@ -22,6 +22,7 @@ EXTRA_FLAGS = {'attention.hip': ['-ffp-contract=off'], 'attention_backward.hip':
                'iou_matrix.hip': ['-ffp-contract=off'],       # x * std + mean <= t as a multiply, an add and a compare, like torch
                'dataset.hip': ['-ffp-contract=off'],          # (v - mean) / std as a subtract and a divide, like numpy
                'optim.hip': ['-ffp-contract=off'],            # Adam's update: the compiler fuses nothing beyond the three explicit fmaf()
+               'refinement_step.hip': ['-ffp-contract=off'],  # network_pred_to_df as an add, a multiply and a divide, like torch; 1 - out^2 is an explicit fmaf()
                'conv3d_mfma.hip': ['-fno-slp-vectorize'], 'conv3d_up.hip': ['-fno-slp-vectorize']}
 
 
@@ -96,7 +97,7 @@ def build(force=False, verbose=False, out=None, extra_flags=(), objdir=None):
                HERE.parents[1] / 'include' / 'rfuse.h', HERE.parents[1] / 'include' / 'rfuse_eval.h', HERE.parents[1] / 'include' / 'rfuse_train.h',
                HERE.parents[1] / 'include' / 'rfuse_contrastive.h', HERE.parents[1] / 'include' / 'rfuse_pairs.h', HERE.parents[1] / 'include' / 'rfuse_attn_train.h',
                HERE.parents[1] / 'include' / 'rfuse_level.h', HERE.parents[1] / 'include' / 'rfuse_data.h',
-               HERE.parents[1] / 'include' / 'rfuse_optim.h']
+               HERE.parents[1] / 'include' / 'rfuse_optim.h', HERE.parents[1] / 'include' / 'rfuse_step.h']
 
     def compile_one(src):
         obj = objdir / (src.replace('.hip', '.o'))

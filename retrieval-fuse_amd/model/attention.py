@@ -220,12 +220,17 @@ class PatchedAttentionBlock(nn.Module):
         self.unfold_3d = Unfold3D(patch_extent, self.nf)
         self.unfold_3d_occ = Unfold3D(patch_extent, 1)
 
-    def get_features(self, x_predicted, x_target, occupancy):
-        """reference :132-139 -> (theta feats [N,32], phi feats [N,32], per-patch occupancy any() [N] bool)."""
+    def get_features(self, x_predicted, x_target, occupancy, occupancy_rows=None):
+        """reference :132-139 -> (theta feats [N,32], phi feats [N,32], per-patch occupancy any() [N] bool).  ``occupancy_rows``: that row vector
+        computed beforehand (rfuse.ops.attn_occupancy_rows, straight from the decoder's prediction); ``occupancy`` is then not looked at."""
         x_predicted_feat_ = self.unfold_3d(x_predicted)
         x_target_feat_ = self.unfold_3d(x_target)
-        occupancy_ = self.unfold_3d_occ(occupancy.to(torch.float32))
         x_feat_flat, p_feat_flat = self.attention_blocks_layer.get_features(x_predicted_feat_, x_target_feat_)
+        if occupancy_rows is not None:
+            if occupancy_rows.numel() != x_predicted_feat_.shape[0]:
+                raise ValueError('get_features: occupancy_rows has %d entries for %d rows' % (occupancy_rows.numel(), x_predicted_feat_.shape[0]))
+            return x_feat_flat, p_feat_flat, occupancy_rows.reshape(-1).ne(0)
+        occupancy_ = self.unfold_3d_occ(occupancy.to(torch.float32))
         occupancy_flat = occupancy_.reshape((x_predicted_feat_.shape[0], -1)).ne(0).any(dim=1)
         return x_feat_flat, p_feat_flat, occupancy_flat
 

@@ -79,7 +79,7 @@ class Superresolution08FinalDecoder(nn.Module):
     """nf x 32^3 -> 1 x 64^3 in (-1,1) (reference model/refinement.py:48-61): DecoderNoJoining, 1x1x1 conv, tanh.
 
     ``forward_df(x, trunc)`` additionally applies network_pred_to_df (trainer/train_refinement.py:242-243) inside the
-    same kernel epilogue."""
+    same kernel epilogue.  Grad mode (rfuse.autograd.PointwiseTanh) takes nf <= 64; a wider head raises NotImplementedError in the forward."""
 
     def __init__(self, nf, layer_order):
         super().__init__()
@@ -88,12 +88,11 @@ class Superresolution08FinalDecoder(nn.Module):
     def forward(self, x):
         if not ops.needs_grad(x, *self.parameters()):
             return self._head(x, 0.0, 1.0)
-        # grad mode (training slice, rfuse/autograd.py): the 16 -> 1 pointwise conv + tanh is 0.1 % of the work and torch differentiates it --
-        # written as a weighted channel sum, not as F.conv3d: that was the one MIOpen call of the path, and its first use runs MIOpen's solver
-        # search (naive_conv_ab_nonpacked_wrw, a batched-GEMM bwd_weight, ...: 2.4 s of kernels before the first step finishes)
-        x = self.network[0](x)
-        w, b = self.network[1].weight, self.network[1].bias
-        return torch.tanh((x.unsqueeze(1) * w.view(1, w.shape[0], w.shape[1], 1, 1, 1)).sum(dim=2) + b.view(1, -1, 1, 1, 1))
+        # grad mode (training slice, rfuse/autograd.py): the up stage through ConvGnRelu, the 16 -> 1 pointwise conv + tanh through PointwiseTanh --
+        # rf_conv1x1_tanh forward, one pass over the head's input backward.  (Neither F.conv3d, the one MIOpen call the path ever had, whose first use
+        # runs MIOpen's solver search, nor a broadcast product that materialises [B, 1, nf, 64^3] forward and backward.)
+        from rfuse import autograd as rf_autograd
+        return rf_autograd.PointwiseTanh.apply(self.network[0](x), self.network[1].weight, self.network[1].bias)
 
     def _head(self, x, post_add, post_mul):
         """the up stage's second conv + the pointwise head (+ network_pred_to_df).  Where the split box kernel takes the conv, the head runs in its epilogue:

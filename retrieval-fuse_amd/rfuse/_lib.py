@@ -1,7 +1,7 @@
 """ctypes binding of librfuse_hip.so (the C ABI declared in include/rfuse.h, the evaluation ABI of include/rfuse_eval.h, the training-loss ABI
 of include/rfuse_train.h, the contrastive-loss ABI of include/rfuse_contrastive.h, the pairwise-occupancy ABI of include/rfuse_pairs.h, the
-attention-backward ABI of include/rfuse_attn_train.h, the level ABI of include/rfuse_level.h, the dataset ABI of include/rfuse_data.h and the
-optimiser ABI of include/rfuse_optim.h).
+attention-backward ABI of include/rfuse_attn_train.h, the level ABI of include/rfuse_level.h, the dataset ABI of include/rfuse_data.h, the
+optimiser ABI of include/rfuse_optim.h and the refinement-step ABI of include/rfuse_step.h).
 
 The argument and return types are read from the header itself at import (``parse_header``): there is no second copy of the ABI to keep
 in step.  There is NO fallback: if the library is missing a RuntimeError is raised, and every entry point that returns a status
@@ -14,7 +14,8 @@ rfuse/losses.py) and ``load_contrastive()`` include/rfuse_contrastive.h (``CONTR
 loss, rfuse/losses.py) and ``load_pairs()`` include/rfuse_pairs.h (``PAIRS_SIGNATURES``: the retrieval trainer's IoU matrix, rfuse/losses.py) and ``load_attn_train()`` include/rfuse_attn_train.h
 (``ATTN_TRAIN_SIGNATURES``: the backward of the patch attention's row route, rfuse/ops.py) and ``load_level()`` include/rfuse_level.h (``LEVEL_SIGNATURES``:
 a whole encoder level in one launch, rfuse/ops.py) and ``load_data()`` include/rfuse_data.h (``DATA_SIGNATURES``: the patch dataset's occupancy counts and batch
-windows, rfuse/data.py) and ``load_optim()`` the ninth header include/rfuse_optim.h (``OPTIM_SIGNATURES``: the multi-tensor Adam step, rfuse/optim.py), all from the
+windows, rfuse/data.py) and ``load_optim()`` the ninth header include/rfuse_optim.h (``OPTIM_SIGNATURES``: the multi-tensor Adam step, rfuse/optim.py) and ``load_step()`` the tenth,
+include/rfuse_step.h (``STEP_SIGNATURES``: the decoder head's backward and the attention rows' occupancy, rfuse/ops.py), all from the
 same shared object, under the same status rule.
 """
 import ctypes
@@ -35,6 +36,7 @@ ATTN_TRAIN_HEADER_PATH = _HERE.parents[1] / 'include' / 'rfuse_attn_train.h'
 LEVEL_HEADER_PATH = _HERE.parents[1] / 'include' / 'rfuse_level.h'
 DATA_HEADER_PATH = _HERE.parents[1] / 'include' / 'rfuse_data.h'
 OPTIM_HEADER_PATH = _HERE.parents[1] / 'include' / 'rfuse_optim.h'
+STEP_HEADER_PATH = _HERE.parents[1] / 'include' / 'rfuse_step.h'
 
 # every scalar type include/rfuse.h uses; any pointer is a c_void_p, and `const char*` as a return type a c_char_p
 _SCALARS = {'int': ctypes.c_int, 'float': ctypes.c_float, 'size_t': ctypes.c_size_t, 'int64_t': ctypes.c_int64, 'long long': ctypes.c_int64}
@@ -90,6 +92,7 @@ ATTN_TRAIN_SIGNATURES = parse_header(ATTN_TRAIN_HEADER_PATH.read_text())
 LEVEL_SIGNATURES = parse_header(LEVEL_HEADER_PATH.read_text())
 DATA_SIGNATURES = parse_header(DATA_HEADER_PATH.read_text())
 OPTIM_SIGNATURES = parse_header(OPTIM_HEADER_PATH.read_text())
+STEP_SIGNATURES = parse_header(STEP_HEADER_PATH.read_text())
 
 
 def is_status(name, table=None):
@@ -113,6 +116,7 @@ _attn_train = None
 _level = None
 _data = None
 _optim = None
+_step = None
 
 
 class _Library:
@@ -230,6 +234,14 @@ def load_optim():
     if _optim is None:
         _optim = _Library(load()._cdll, OPTIM_SIGNATURES)
     return _optim
+
+
+def load_step():
+    """The entry points of include/rfuse_step.h, bound like ``load_eval()``'s (its ``start_profile`` brackets them)."""
+    global _step
+    if _step is None:
+        _step = _Library(load()._cdll, STEP_SIGNATURES)
+    return _step
 
 
 def check(rc, what):

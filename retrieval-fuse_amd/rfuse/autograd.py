@@ -27,11 +27,14 @@ retrieval_backbone / attention parameters, :295-306 phase hand-over).  Built her
       forward   rf_attn_fuse (the inference kernel; only its inputs are saved)
       backward  rf_attn_fuse_backward: one launch for dx, dp and the gradients of the RAW encoder outputs; the row's decisions are recomputed with the
                 forward's code; the switch's gradient goes to the first maximal score like MaxPool1d(K); Gumbel-hard as torch's straight-through form
+  PointwiseTanh   y = tanh(conv1x1(x, W) + b)   the final decoder's head (reference model/refinement.py:54-55)
+      forward   rf_conv1x1_tanh (the inference kernel: the same bits as the plain inference route)
+      backward  rf_pointwise_tanh_backward (include/rfuse_step.h): dx, dW, db from the saved output in one pass over x, float64 sums in a fixed order
   Unfold3d / Fold3d / GatherRetrieved   rf_unfold3d <-> rf_fold3d, rf_attn_gather_retrieved -> rf_attn_scatter_retrieved (pure index maps, same bits as
                 the permuted views they replace)
 
 torch does the bookkeeping and the light per-row work: transposes / flips of weights, the activation mask of Linear, sums over the batch of
-per-sample float64 pieces, the 16 -> 1 pointwise conv + tanh of the final decoder and the Gumbel noise draw -- together < 1 % of the FLOPs.  With
+per-sample float64 pieces and the Gumbel noise draw -- together < 1 % of the FLOPs.  With
 that the whole training graph of the reference (trainer/train_refinement.py:108-116 forward_full, all four networks trainable = phase 3) runs
 through the drop-in modules in grad mode; loss and every parameter gradient are checked against float64 autograd of the oracle in
 tests/test_autograd_gpu.py.  Not built: backward of the pre-split pair routes and the fused attention MLP (grad mode takes the plain routes), the
@@ -171,16 +174,25 @@ class ConvGnRelu(torch.autograd.Function):
         x, gamma, weight, aff, y = ctx.saved_tensors
         n, cin, edge = x.shape[0], x.shape[1], x.shape[2]
         cout = weight.shape[0]
+        # what nobody asked for is not computed (a frozen network inside a training step: no weight-gradient launches; an input that is data: no
+        # data gradient); what is asked for keeps its bits.  GroupNorm's backward gives dx, dgamma and dbeta together and needs the data gradient.
+        need_x, need_gamma, need_beta, need_w = ctx.needs_input_grad[:4]
+        need_dgrad = need_x or need_gamma or need_beta
+        if not (need_dgrad or need_w):
+            return (None,) * 8
         with torch.no_grad():
             inv_s = scales = None
-            use_dgrad = edge >= 4 and dgrad_split_supported(y, weight, cin)
-            use_wgrad = ctx.split_ok and y.numel() % 4 == 0 and bool(_lib.load().rf_conv3d_k3_wgrad_split_supported(cin, cout, n, edge))
+            use_dgrad = need_dgrad and edge >= 4 and dgrad_split_supported(y, weight, cin)
+            use_wgrad = need_w and ctx.split_ok and y.numel() % 4 == 0 and bool(_lib.load().rf_conv3d_k3_wgrad_split_supported(cin, cout, n, edge))
             if use_dgrad or use_wgrad:
                 dz, amax = relu_backward_amax(dy.contiguous(), y)
                 ident, scales = dz_scale(amax, n, cout)
             else:
                 dz = relu_backward(dy.contiguous(), y) if y.numel() % 4 == 0 else dy * (y > 0)
-            if use_dgrad:
+            dxn = dw = None
+            if not need_dgrad:
+                pass
+            elif use_dgrad:
                 dxn, inv_s = dgrad_split(dz, ident, weight, cin), scales[1:]
             elif edge >= 2:
                 wt = weight.flip(2, 3, 4).transpose(0, 1).contiguous()          # [cin, cout, 3,3,3]: the data-gradient conv's weight
@@ -189,7 +201,9 @@ class ConvGnRelu(torch.autograd.Function):
                 dxn = conv3d_gn(dz, ident, ops.pack_conv3_weight(wt), cin, relu=False)
             else:                                                                   # 1^3 volume: only the centre tap touches data
                 dxn = ops.linear(dz.reshape(n, cout), ops.pack_linear_weight(weight[:, :, 1, 1, 1].t().contiguous()), None, cin).reshape(n, cin, 1, 1, 1)
-            if use_wgrad:
+            if not need_w:
+                pass
+            elif use_wgrad:
                 dw = conv3d_wgrad_split(x, aff, dz, scales, cout)
             elif edge >= 4:
                 dw = conv3d_wgrad(x, aff, dz, cout)
@@ -201,8 +215,10 @@ class ConvGnRelu(torch.autograd.Function):
                 dzf = dz.permute(0, 2, 3, 4, 1).reshape(n * edge ** 3, cout)
                 dw = ops.linear_wgrad(dzf.contiguous(), cols.contiguous()).reshape(cout, cin, 3, 3, 3)
             # (d xn of the split data gradient came scaled by s: GroupNorm backward is linear in it and takes 1 / s out)
-            dx, dgamma, dbeta = gn_backward(x, dxn.contiguous(), gamma, ctx.groups, ctx.eps, inv_s)
-        return dx, dgamma, dbeta, dw, None, None, None, None
+            dx = dgamma = dbeta = None
+            if need_dgrad:
+                dx, dgamma, dbeta = gn_backward(x, dxn.contiguous(), gamma, ctx.groups, ctx.eps, inv_s)
+        return (dx if need_x else None, dgamma if need_gamma else None, dbeta if need_beta else None, dw, None, None, None, None)
 
 
 class Linear(torch.autograd.Function):
@@ -223,10 +239,35 @@ class Linear(torch.autograd.Function):
                 dpre = dy.contiguous()
             else:                                                   # y > 0 <=> pre-activation > 0 for ReLU and LeakyReLU(slope > 0)
                 dpre = torch.where(y > 0, dy, dy * (ctx.slope if ctx.act == ops.ACT_LEAKY else 0.0)).contiguous()
-            dx = ops.linear(dpre, ops.pack_linear_weight(weight.t().contiguous()), None, weight.shape[1])
-            dw = ops.linear_wgrad(dpre, x)
-            db = dpre.double().sum(0).float() if ctx.has_bias else None
+            need_x, need_w, need_b = ctx.needs_input_grad[:3]
+            dx = ops.linear(dpre, ops.pack_linear_weight(weight.t().contiguous()), None, weight.shape[1]) if need_x else None
+            dw = ops.linear_wgrad(dpre, x) if need_w else None
+            db = dpre.double().sum(0).float() if ctx.has_bias and need_b else None
         return dx, dw, db, None, None
+
+
+class PointwiseTanh(torch.autograd.Function):
+    """the final decoder's head, tanh(Conv3d(nf, 1, 1)): rf_conv1x1_tanh forward (the inference kernel), rf_pointwise_tanh_backward backward.  x and the
+    output are saved; nothing of the size of [B, 1, nf, 64^3] is ever materialised.  At most 64 channels and a multiple of four voxels, checked in the
+    forward.  A frozen head (neither weight nor bias asks for a gradient) costs the data gradient alone: no sums, no second launch."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        x = x.contiguous()
+        if not ops.pointwise_tanh_supported(x.shape[0], x.shape[1], x[0, 0].numel()):
+            raise NotImplementedError('PointwiseTanh: %s is outside what its backward supports (1 <= channels <= 64, voxels %% 4 == 0)' % (tuple(x.shape),))
+        with torch.no_grad():
+            y = ops.conv1x1_tanh(x, weight, bias)
+        ctx.save_for_backward(x, weight, y)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight, y = ctx.saved_tensors
+        need_x, need_w, need_b = ctx.needs_input_grad
+        with torch.no_grad():
+            dx, dw, db = ops.pointwise_tanh_backward(x, y, dy.contiguous(), weight, sums=need_w or need_b)
+        return dx if need_x else None, dw if need_w else None, db if need_b else None
 
 
 class AttnFuse(torch.autograd.Function):

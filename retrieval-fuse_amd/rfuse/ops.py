@@ -760,6 +760,52 @@ def conv1x1_tanh(x, w, b, post_add=0.0, post_mul=1.0):
     return out
 
 
+def pointwise_tanh_supported(n, c, voxels):
+    """what ``pointwise_tanh_backward`` takes: voxels % 4 == 0, 1 <= c <= 64"""
+    return int(_lib.load_step().rf_pointwise_tanh_backward_ws_bytes(n, c, voxels)) != 0
+
+
+def pointwise_tanh_backward(h, out, dout, w, sums=True):
+    """backward of ``conv1x1_tanh`` (post_add 0, post_mul 1; include/rfuse_step.h): h [n,c,...] the head's input, out / dout [n,1,...] the saved tanh
+    output and its gradient, w [1,c,1,1,1] -> dh like h, dw like w, db [1].  Two launches, the same bits on every call.  ``sums=False`` (a frozen
+    head): dh alone, one launch, dw and db come back as None."""
+    _req(h, 'h'), _req(out, 'out'), _req(dout, 'dout'), _req(w.detach(), 'w')
+    n, c = h.shape[0], h.shape[1]
+    vox = h[0, 0].numel()
+    if w.numel() != c or out.numel() != n * vox or dout.numel() != n * vox:
+        raise ValueError('pointwise_tanh_backward: h %s, out %s, dout %s, w %s do not belong together' % (tuple(h.shape), tuple(out.shape), tuple(dout.shape), tuple(w.shape)))
+    lib = _lib.load_step()
+    nbytes = int(lib.rf_pointwise_tanh_backward_ws_bytes(n, c, vox))
+    if nbytes == 0:
+        raise NotImplementedError('pointwise_tanh_backward: %s is outside the supported range (voxels %% 4 == 0, 1 <= channels <= 64)' % (tuple(h.shape),))
+    dh = torch.empty_like(h)
+    if not sums:
+        lib.rf_pointwise_tanh_backward(_p(h), _p(out), _p(dout), _p(w.detach()), n, c, vox, _p(dh), _p(None), _p(None), _p(None), 0, _stream())
+        return dh, None, None
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=h.device)
+    dw = torch.empty(w.shape, dtype=torch.float32, device=h.device)
+    db = torch.empty(1, dtype=torch.float32, device=h.device)
+    lib.rf_pointwise_tanh_backward(_p(h), _p(out), _p(dout), _p(w.detach()), n, c, vox, _p(dh), _p(dw), _p(db), _p(ws), nbytes, _stream())
+    return dh, dw, db
+
+
+def attn_occupancy_rows(pred, trunc, thr, e):
+    """pred [n,1,S,S,S] (the decoder's tanh output) -> bool [n * (S / 2e)^3], the patch attention's per-row occupancy in Unfold3D(e)'s row order: what
+    trainer/train_refinement.py:242-247 (network_pred_to_df, ``<= thr``, max_pool3d(2), bool) and model/attention.py:135-138 (unfold, any) give, exactly.
+    ``trunc`` / ``thr``: Python scalars, taken as the float32 values torch gives them beside a float32 tensor.  One launch."""
+    _req(pred, 'pred')
+    if pred.dim() != 5 or pred.shape[1] != 1 or not (pred.shape[2] == pred.shape[3] == pred.shape[4]):
+        raise ValueError('attn_occupancy_rows: expected a [n, 1, S, S, S] prediction, got %s' % (tuple(pred.shape),))
+    n, s, e = pred.shape[0], pred.shape[2], int(e)
+    if n < 1 or e < 1 or s < 1 or s % (2 * e):
+        raise ValueError('attn_occupancy_rows: edge %d is no multiple of 2 * %d (n = %d)' % (s, e, n))
+    r = s // (2 * e)
+    rows = torch.empty(n * r * r * r, dtype=torch.bool, device=pred.device)
+    f32 = lambda v: float(torch.tensor(float(v), dtype=torch.float32))
+    _lib.load_step().rf_attn_occupancy_rows(_p(pred), n, s, e, f32(trunc), f32(thr), _p(rows), _stream())
+    return rows
+
+
 def pack_convv_weight(w):
     _req(w.detach(), 'conv weight')
     return _pack_weight('convv', w, tuple(w.shape[:3]))
